@@ -15,6 +15,12 @@ scaling: every rank encodes B closed-GOP segments of F frames per step.  A timed
 
 bracketed by barrier + torch.cuda.synchronize(); the step time is the max over ranks.
 The reference publishes no numbers, so vs_baseline is null.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the result line.  ``--full``
+adds what the headline does not need: PSNR/SSIM of the first warmup step, per-stage device
+times of the warmup steps and the merged stream's SHA-256.  ``--dump-outputs DIR`` writes what
+the last timed step produced as ``DIR/<name>.npy`` (rank 0), so two builds can be compared
+output for output: the inputs depend on the arguments only.
 """
 from __future__ import annotations
 
@@ -60,6 +66,37 @@ def _memory(env, merged) -> dict:
             "merge_bytes_per_step": int(len(merged)) if merged is not None else 0}
 
 
+DUMP_SAMPLE = 1 << 22  # bytes of the merged stream kept by --dump-outputs (16 MB as float32)
+
+
+def dump_outputs(path: str, res, merged) -> None:
+    """The last timed step's outputs as float .npy files (rank 0):
+
+    * ``nal_bytes`` [segments, pictures + 1], float64: rank 0's segments, the size of each one's
+      parameter sets, then of every slice NAL in coding order;
+    * ``segment_sha48`` [segments], float64: the first 48 bits of each of those segments'
+      SHA-256 (exact in a double; any changed byte changes it);
+    * ``merged_sample`` [min(len, DUMP_SAMPLE)], float32: the whole node's merged Annex-B stream
+      at fixed positions (seeded, in stream order; positions scale with the stream's length),
+      the whole stream when it is shorter than the sample."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    n = max(len(r.nals) for r in res)
+    sizes = np.zeros((len(res), n + 1), dtype=np.float64)
+    for b, r in enumerate(res):
+        sizes[b, 0] = len(r.header)
+        sizes[b, 1:len(r.nals) + 1] = [len(x) for x in r.nals]
+    np.save(os.path.join(path, "nal_bytes.npy"), sizes)
+    sha = [int.from_bytes(hashlib.sha256(r.bitstream).digest()[:6], "big") for r in res]
+    np.save(os.path.join(path, "segment_sha48.npy"), np.asarray(sha, dtype=np.float64))
+    stream = np.asarray(merged if merged is not None else [], dtype=np.uint8)
+    if len(stream) > DUMP_SAMPLE:
+        pos = np.sort(np.random.default_rng(20240229).random(DUMP_SAMPLE))
+        stream = stream[(pos * len(stream)).astype(np.int64)]
+    np.save(os.path.join(path, "merged_sample.npy"), stream.astype(np.float32))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -85,12 +122,18 @@ def main() -> None:
     ap.add_argument("--json-out", default=None)
     ap.add_argument("--merged-out", default=None,
                     help="rank 0 writes the last timed step's merged Annex-B stream here")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: PSNR/SSIM of the first warmup step, "
+                         "per-stage device times of the warmup steps, SHA-256 of the merged stream")
     ap.add_argument("--no-quality", dest="quality", action="store_false",
-                    help="skip the PSNR/SSIM measurement of the first warmup step")
+                    help="with --full: skip the PSNR/SSIM measurement of the first warmup step")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the last timed step's outputs as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--allow-knobs", action="store_true",
                     help="apply MIVC_* encoder / bench knobs from the environment (refused otherwise); "
                          "every applied value is reported under config.env")
     a = ap.parse_args()
+    a.quality = a.quality and a.full
     from govideocompressor_amd.models import knobs as K
     env_knobs = K.check_environment(a.allow_knobs)
 
@@ -177,16 +220,17 @@ def main() -> None:
         merged = fut.result()
         return first_res, res, merged
 
-    # PSNR/SSIM are measured on the (untimed) first warmup step: quality measurement is not
-    # part of encoding (an ffmpeg/x264 encode computes none unless asked); the timed steps
+    # --full: PSNR/SSIM are measured on the (untimed) first warmup step: quality measurement is
+    # not part of encoding (an ffmpeg/x264 encode computes none unless asked); the timed steps
     # encode the same content distribution (new seed per step).
     qres = None
     stage_ms = {}
     if a.warmup:
-        # per-stage device time (HIP events + roctx ranges) on the untimed warmup only
-        enc.stage_timer.enabled = True
+        # --full: per-stage device time (HIP events + roctx ranges) on the untimed warmup only
+        enc.stage_timer.enabled = a.full
         qres, _, _ = run_steps(-100, a.warmup, metrics_first=a.quality)
-        stage_ms = {k: round(v["s"] * 1000.0 / a.warmup, 2) for k, v in enc.stage_timer.summary().items()}
+        if a.full:
+            stage_ms = {k: round(v["s"] * 1000.0 / a.warmup, 2) for k, v in enc.stage_timer.summary().items()}
         enc.stage_timer.enabled = False
         # the timed loop keeps two input batches alive (step k encodes while k + 1 is
         # synthesized): let the caching allocator map the second one (on the synthesis
@@ -209,6 +253,8 @@ def main() -> None:
     fps = total_frames / elapsed
     # quality of the warmup step, rate of the last timed step (this rank), averaged over ranks
     q = qres if (qres is not None and a.quality) else None
+    not_asked = "n/a (not asked for: --full)"
+    q_where = "first warmup step (untimed)" if q else ("n/a (no warmup step)" if a.quality else not_asked)
     psnr = D.sum_over_ranks(env, sum(r.psnr_y for r in q) / len(q) if q else 0.0) / env.world
     ssim = D.sum_over_ranks(env, sum(r.ssim_y for r in q) / len(q) if q else 0.0) / env.world
     nbytes = D.sum_over_ranks(env, float(sum(r.nbytes() for r in res)))
@@ -221,6 +267,7 @@ def main() -> None:
             "n_gpus": env.world,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": a.full,
             "ms_per_step": round(elapsed / a.steps * 1000.0, 2),
             "higher_is_better": True,
             "scaling": "weak",
@@ -245,20 +292,22 @@ def main() -> None:
                 "entropy_threads": enc.entropy_threads,
             },
             "quality": {"psnr_y_db": round(psnr, 3), "ssim_y": round(ssim, 4), "bitrate_kbps": round(kbps, 1),
-                        "measured_on": "first warmup step (untimed)" if q else "n/a (no warmup step)",
+                        "measured_on": q_where,
                         "merged_bytes": len(merged) if merged is not None else 0,
-                        # identity of the last timed step's merged stream (same seed: byte-identity
-                        # check of kernel changes, tools/gpu/ab_steps.sh)
+                        # --full: identity of the last timed step's merged stream (same seed:
+                        # byte-identity check of kernel changes, tools/gpu/ab_steps.sh)
                         "merged_sha256_16": hashlib.sha256(memoryview(merged)).hexdigest()[:16]
-                        if merged is not None else None},
+                        if (a.full and merged is not None) else None},
             "timings_rank0_s": {k: round(v, 3) for k, v in enc.timings.items()},
             # interval between consecutive timed steps' completion on rank 0 (the first includes
             # the first input's synthesis and lookahead; the last is not shortened by the merge)
             "step_wall_ms_rank0": [round(1000.0 * (b - a_), 1) for a_, b in zip(step_wall, step_wall[1:])],
-            "stage_device_ms_per_step_rank0": {"measured_on": "warmup steps (untimed)", **stage_ms},
+            "stage_device_ms_per_step_rank0": {"measured_on": "warmup steps (untimed)" if a.full else not_asked, **stage_ms},
             "encoder_stats_rank0": {k: round(v, 4) for k, v in enc.stats.items()},
             "memory_rank0": _memory(env, merged),
         }
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, res, merged)
         if a.merged_out and merged is not None:
             with open(a.merged_out, "wb") as f:
                 f.write(memoryview(merged))

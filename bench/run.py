@@ -112,11 +112,12 @@ def config1(args) -> list[dict]:
 
 
 def config2(args) -> list[dict]:
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(args.steps), "--warmup", str(args.warmup)]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", str(args.steps), "--warmup",
+           str(args.warmup)]
     if args.gpus > 1:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr=127.0.0.1", "--master-port=29511", os.path.join(ROOT, "bench.py"), "--gpus",
-               str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup)]
+               str(args.gpus), "--full", "--steps", str(args.steps), "--warmup", str(args.warmup)]
     out = subprocess.run(cmd, capture_output=True, text=True, check=True).stdout.strip().splitlines()[-1]
     rec = json.loads(out)
     rec["config"] = 2

@@ -8,7 +8,7 @@ extra=""; if [ $# -gt 4 ]; then shift 4; extra="$*"; fi
 mkdir -p $out
 for v in $vals; do
   for crf in $crfs; do
-    env $var=$v timeout -k 10 200 python bench.py --steps 1 --warmup 1 --slots 64 --crf $crf $extra > $out/${var}_${v}_${crf}.log 2>&1 || exit 1
+    env $var=$v timeout -k 10 200 python bench.py --full --steps 1 --warmup 1 --slots 64 --crf $crf $extra > $out/${var}_${v}_${crf}.log 2>&1 || exit 1
     echo "$var=$v $crf $(tail -1 $out/${var}_${v}_${crf}.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); q=d["quality"]; print(q["bitrate_kbps"], q["psnr_y_db"], d["value"])')" >> $out/summary.txt
   done
 done
