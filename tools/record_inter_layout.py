@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""Record the golden bitstream hashes of tests/test_gpu_inter_layout.py.
+
+The test pins the bytes of small encodes, at shapes where the lane layout of encode_inter_mb
+can go wrong, to what the *parent* build of the kernels emits.  So this recorder never runs on
+the kernels under test: it needs MIVC_HIP_LIB to name a kernel library built from the parent
+commit, e.g.
+
+    python tools/build_variant.py parent --rev HEAD~1
+    MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py tests/golden/inter_layout_parent.json
+
+The file holds, per case, the arguments (size, frames, clip seed / class, H264Params overrides)
+and the SHA-256 of every slot's bitstream.  Per case it also prints what the test asserts from
+the decoded records (split partitions, waves of four MBs mixing intra and inter MBs, waves
+mixing MBs with and without the 8x8 transform), so a case that would pass vacuously shows here.
+"""
+from __future__ import annotations
+
+import hashlib
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SLOTS = 2
+_B3 = dict(bframes=3, weightb=True)
+_P = dict(bframes=0)
+_PART = dict(partitions=True, part_overhead=0, part_min_satd=0)
+# size -> nmb % 4: 48x48 -> 9 MBs (one live MB in the last wave), 96x48 -> 18 (two), 80x48 -> 15
+# (three, and 5 MBs per row: waves straddle MB rows), 176x144 -> 99 (baseline)
+CASES = [
+    dict(id="48x48-p-t8-trellis2", width=48, height=48, frames=5, seed=3, kind="default",
+         params=dict(crf=None, qp=24, t8x8=True, trellis=2, aq_strength=0.0, **_P)),
+    dict(id="48x48-b-not8-trellis0", width=48, height=48, frames=9, seed=4, kind="default",
+         params=dict(crf=None, qp=26, t8x8=False, trellis=0, aq_strength=0.0, **_B3)),
+    dict(id="96x48-b-t8-trellis2-aq", width=96, height=48, frames=7, seed=5, kind="default",
+         params=dict(crf=None, qp=26, t8x8=True, trellis=2, aq_strength=1.0, **_B3)),
+    dict(id="96x48-p-refs3-weightp", width=96, height=48, frames=6, seed=6, kind="fade",
+         params=dict(crf=None, qp=26, t8x8=False, trellis=2, aq_strength=0.0, refs=3, weightp=True, **_P)),
+    dict(id="80x48-b-t8-trellis0-part", width=80, height=48, frames=9, seed=7, kind="default",
+         params=dict(crf=None, qp=24, t8x8=True, trellis=0, aq_strength=0.0, **_B3, **_PART)),
+    dict(id="80x48-p-t8-trellis2-aq", width=80, height=48, frames=5, seed=8, kind="default",
+         params=dict(crf=None, qp=28, t8x8=True, trellis=2, aq_strength=1.0, **_P)),
+    dict(id="80x48-p-noise-lowqp", width=80, height=48, frames=6, seed=9, kind="noise",
+         params=dict(crf=None, qp=18, t8x8=True, trellis=2, aq_strength=1.0, **_P)),
+    dict(id="176x144-p-part", width=176, height=144, frames=9, seed=3, kind="default",
+         params=dict(crf=None, qp=24, t8x8=True, trellis=2, **_P, **_PART)),
+    dict(id="176x144-b-refs3-weightp-aq", width=176, height=144, frames=9, seed=10, kind="default",
+         params=dict(crf=None, qp=26, t8x8=True, trellis=2, aq_strength=1.0, refs=3, weightp=True, **_B3)),
+    dict(id="176x144-b-noise-lowqp", width=176, height=144, frames=9, seed=11, kind="noise",
+         params=dict(crf=None, qp=16, t8x8=True, trellis=2, aq_strength=1.0, **_B3)),
+]
+
+INTRA_KINDS = (0, 1, 4, 8)
+SPLIT_KINDS = (5, 6, 7, 10, 11, 12)
+
+
+def encode_case(case):
+    """-> (encoder, results); the caller closes the encoder."""
+    import torch
+    from govideocompressor_amd.models.h264_gpu import GpuH264Encoder, H264Params, synth_clip
+
+    p = H264Params(width=case["width"], height=case["height"], **case["params"])
+    enc = GpuH264Encoder(p, slots=SLOTS)
+    y, u, v = synth_clip(SLOTS, case["frames"], case["width"], case["height"], seed=case["seed"], kind=case["kind"])
+    res = enc.encode(y, u, v, keep_recon=True)
+    torch.cuda.synchronize()
+    return enc, res
+
+
+def record_stats(host, bitstreams):
+    """What the decoded records say about the waves of encode_inter_mb (four consecutive MBs of
+    a P / B picture): split partition MBs, waves with intra and inter MBs, waves with inter MBs
+    on and off the 8x8 transform, MB QPs per picture."""
+    import numpy as np
+
+    out = dict(split=0, mixed_intra=0, mixed_t8=0, qps=0)
+    for seg in host.parse(list(bitstreams), 1):
+        for hdr in np.asarray(seg["hdr"]):
+            kind, flags, qp = hdr[:, 0], hdr[:, 5], hdr[:, 2]
+            intra = np.isin(kind, INTRA_KINDS)
+            if intra.all():
+                continue
+            out["split"] += int(np.isin(kind, SPLIT_KINDS).sum())
+            out["qps"] = max(out["qps"], int(np.unique(qp[~intra]).size))
+            t8 = (flags & 2) != 0
+            for w0 in range(0, kind.size, 4):
+                i, t = intra[w0:w0 + 4], t8[w0:w0 + 4]
+                out["mixed_intra"] += int(i.any() and not i.all())
+                out["mixed_t8"] += int((t & ~i).any() and (~t & ~i).any())
+    return out
+
+
+def main() -> None:
+    if len(sys.argv) != 2:
+        raise SystemExit(__doc__)
+    lib = os.environ.get("MIVC_HIP_LIB")
+    if not lib or not os.path.exists(lib):
+        raise SystemExit("MIVC_HIP_LIB must name a kernel library built from the parent commit")
+    from govideocompressor_amd.ops import native
+
+    host = native.host()
+    rows = []
+    for case in CASES:
+        enc, res = encode_case(case)
+        streams = [bytes(r.bitstream) for r in res]
+        enc.close()
+        print(case["id"], [len(s) for s in streams], record_stats(host, streams), flush=True)
+        rows.append(dict(case, sha256=[hashlib.sha256(s).hexdigest() for s in streams]))
+    with open(sys.argv[1], "w") as f:
+        json.dump(dict(slots=SLOTS, cases=rows), f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
