@@ -20,6 +20,7 @@
 //   cavlc_offsets   (B, 1024)                 prefix sum of lengths, header + trailer bits
 //   cavlc_write     (nmb x B, wave64 per MB)  emit bits (lanes own disjoint bit ranges)
 //   cavlc_compact   (B, 256)                  big-endian words -> bytes, packed slot after slot
+#include "h264_mvpred.h"
 #include "kcommon.h"
 
 namespace mivc {
@@ -219,8 +220,6 @@ __device__ __forceinline__ void load16(const int16_t* p, int (&v)[16]) {
 }
 
 // ---------------------------------------------------------------- helpers
-__device__ __forceinline__ int med3(int a, int b, int c) { return max(min(a, b), min(max(a, b), c)); }
-
 struct NbMv {
   bool avail;
   int ref;

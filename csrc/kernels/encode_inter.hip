@@ -10,6 +10,7 @@
 // SURVEY.md K-C8.  One wave64 per four macroblocks: luma on all 64 lanes (one 16-lane row
 // per MB, a lane per 4x4 block), then chroma on 32 lanes (see encode_inter_mb).
 #include "h264_trellis.h"
+#include "mb_row.h"
 
 namespace mivc {
 namespace gpu {
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
   const size_t rcur = route_index(a.rt, a.nbuf, slot, RO_CUR);
   const int W = g.W, cw = g.cw(), CH = g.ch();
   // the wave's first MB (always inside the picture); MB qi follows it in raster order
-  const int mb0 = ux * 4, mx0 = mb0 % g.wmb, my0 = mb0 / g.wmb;
+  const int mb0 = ux * kMbsPerWave, mx0 = mb0 % g.wmb, my0 = mb0 / g.wmb;
   // MB qi of the wave (the tail's dead lanes are clamped to the last MB): position, record
   // index, inter-coded here (work), QP.  With adaptive quantisation the four MBs have four
   // QPs: every lane fetches its own MB's table rows (one address, 3-dword loads) -- fewer
@@ -185,8 +186,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
 
   // 8x8 transform path (a.t8): the luma source / prediction samples (sa8d operands) and the
   // 8x8 transform buffers (residual -> coefficients, later dequantised levels -> residual)
-  __shared__ uint32_t s_px[4][2][16][4];  // [MB][source / prediction][row][dword]
-  __shared__ int s_d8[4][4][64];          // [MB][8x8 block][raster]
+  __shared__ uint32_t s_px[kMbsPerWave][2][16][4];  // [MB][source / prediction][row][dword]
+  __shared__ int s_d8[kMbsPerWave][4][64];          // [MB][8x8 block][raster]
 
   auto store_levels = [](int16_t* dst, const int* v) {  // 16 levels, 16-byte aligned
     uint32_t w[8];
@@ -698,5 +699,5 @@ extern "C" void mivc_launch_encode_inter(int B, int wmb, int hmb, const uint8_t*
   a.ref1_v = ref1_v;
   a.bmode = bmode;
   a.t8 = t8;
-  hipLaunchKernelGGL(encode_inter_mb, dim3((wmb * hmb + 3) / 4, B), dim3(64), 0, static_cast<hipStream_t>(stream), a);
+  hipLaunchKernelGGL(encode_inter_mb, dim3(mb_row_grid(wmb * hmb), B), dim3(64), 0, static_cast<hipStream_t>(stream), a);
 }

@@ -105,7 +105,7 @@ __device__ __forceinline__ int satd4x4_u8(const uint32_t (&s)[4], const uint32_t
 // cache write-back/invalidate (agent-scope fences cost 1.7-7 us per hand-off on
 // MI355X, guide §Persistent kernels price list; the first version of these
 // kernels spent ~20 us per MB step there).
-constexpr int kMaxRows = 272;
+constexpr int kMaxRows = 272;  // 8K: 4320 / 16 = 270 MB rows
 
 // Keep memory freed with hipFreeAsync in the device's default pool (release threshold
 // "never"): by default the pool hands it back to the driver at every synchronisation, and
@@ -121,7 +121,7 @@ inline void keep_async_pool() {
     (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &thr);
   }
   done[dev] = true;
-}  // 8K: 4320 / 16 = 270 MB rows
+}
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
@@ -269,11 +269,6 @@ __device__ __forceinline__ int min64(int v) {
   return min(static_cast<int>(q[0]), static_cast<int>(q[1]));
 }
 
-// ---------------------------------------------------------------- lane-parallel 4x4 transforms
-// A 4x4 block lives in a group of 4 consecutive lanes (base = lane & ~3); lane base+y
-// holds row y in v[0..3].  Row passes are in-register, column passes exchange the
-// group's rows with DPP quad broadcasts.  Every lane of the wave must execute these
-// (uniform control flow) because shuffles read other lanes' registers.
 // XCD-aware workgroup order for (x = unit within a slot, y = slot) grids: the hardware
 // deals workgroups round-robin over the 8 XCDs, so consecutive units (neighbouring MBs,
 // whose reference rows overlap) would land on 8 different L2s and every cache line would
@@ -286,6 +281,11 @@ __device__ __forceinline__ void xcd_unit_slot(int& x, int& y) {
   x = lin - y * gx;
 }
 
+// ---------------------------------------------------------------- lane-parallel 4x4 transforms
+// A 4x4 block lives in a group of 4 consecutive lanes (base = lane & ~3); lane base+y
+// holds row y in v[0..3].  Row passes are in-register, column passes exchange the
+// group's rows with DPP quad broadcasts.  Every lane of the wave must execute these
+// (uniform control flow) because shuffles read other lanes' registers.
 __device__ __forceinline__ int sel4(int y, int a, int b, int c, int d) { return y == 0 ? a : (y == 1 ? b : (y == 2 ? c : d)); }
 
 // forward integer core transform (encoder side)
@@ -350,10 +350,6 @@ __device__ __forceinline__ int pos_class(int x, int y) {
 // (x = -1 .. 19, top-right included), column 0 = the column to its left.
 constexpr int kTileStride = 24;
 
-// Intra4x4 neighbour vector e[13] of block blk (see h264::i4_pred_sample) + availability
-// Intra4x4 neighbour vector e[0..12] of block blk (0: top-left, 1-8: above and above-right,
-// 9-12: left) from the tile: lane i < 13 returns entry i (the other lanes 0) -- one register
-// per lane instead of the 13-entry vector in every lane.  *av_out: availability (uniform).
 // luma4x4BlkIdx <-> 4x4 block column / row and raster index, by bit arithmetic (a table lookup
 // with a run-time index is a memory load on the dependency chain of every block)
 __device__ __forceinline__ int blkidx_x(int b) { return (b & 1) | ((b >> 1) & 2); }
@@ -363,6 +359,10 @@ __device__ __forceinline__ int raster_to_blkidx(int r) {
   return (x & 1) | ((y & 1) << 1) | ((x & 2) << 1) | ((y & 2) << 2);
 }
 
+// Intra4x4 neighbour vector e[0..12] of block blk (see h264::i4_pred_sample; 0: top-left, 1-8:
+// above and above-right, 9-12: left) from the tile: lane i < 13 returns entry i (the other
+// lanes 0) -- one register per lane instead of the 13-entry vector in every lane.  *av_out:
+// availability (uniform).
 __device__ __forceinline__ int i4_neighbour_lane(const uint8_t* t, int blk, int mbav, int lane, int* av_out) {
   int bx = blkidx_x(blk), by = blkidx_y(blk);
   bool left = bx > 0 || (mbav & h264::AV_LEFT), top = by > 0 || (mbav & h264::AV_TOP);

@@ -33,6 +33,7 @@
 // operand (H64, 4 row tiles of 16) is generated in registers.  SADs of the search
 // are summed over the four row groups of a column with two v_permlane{16,32}_swap.
 #include "kcommon.h"
+#include "qpel.h"
 
 namespace mivc {
 namespace gpu {
@@ -563,9 +564,8 @@ __global__ __launch_bounds__(256) void la_multi(LaMultiArgs a) {
     const int cx0 = clampi(v1x, -8, 8), cy0 = clampi(v1y, -8, 8);  // la_cost's range: |v1| <= 8
     const uint4 p0 = la_raw8(r0, g.ls, X0 + cx0, ry + cy0);
     const uint4 p1 = la_raw8(r1, g.ls, X0 + mx, ry + my);
-    auto avg = [](uint32_t x, uint32_t y) { return (x | y) - (((x ^ y) >> 1) & 0x7F7F7F7Fu); };
-    const int cbi = satd_mfma(negH, accS, as_s8(avg(p0.x, p1.x), avg(p0.y, p1.y), avg(p0.z, p1.z), avg(p0.w, p1.w))) +
-                    2 * (abs(mx) + abs(my) + abs(v1x) + abs(v1y));
+    const uint4 bi = make_uint4(avg4b(p0.x, p1.x), avg4b(p0.y, p1.y), avg4b(p0.z, p1.z), avg4b(p0.w, p1.w));
+    const int cbi = satd_mfma(negH, accS, as_s8(bi.x, bi.y, bi.z, bi.w)) + 2 * (abs(mx) + abs(my) + abs(v1x) + abs(v1y));
     const int bc = min(min(intra, inter1), min(c1, cbi));
     const int s = sum64(mine ? bc : 0);
     const int ni = sum64(mine && intra < min(inter1, min(c1, cbi)) ? 1 : 0);

@@ -20,6 +20,7 @@
 // One wave64 per macroblock; the workgroup id is remapped so each XCD walks a
 // contiguous run of MBs (window rows are shared through that XCD's L2).
 #include "kcommon.h"
+#include "qpel.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -61,10 +62,6 @@ struct MeArgs {
   const int16_t* seed_mv;
 };
 
-constexpr int kNoCost = 0x3FFFFFFF;
-
-constexpr int kHpM = 4;  // half-sample plane margin (samples); coordinates clamp into it exactly
-
 constexpr int kMaxR = 16;
 constexpr int kML = 4;                                   // window margin left/top (6-tap + qpel)
 constexpr int kMR = 6;                                   // margin right/bottom
@@ -84,17 +81,6 @@ __constant__ short kQOff[16][2] = {
     {QO(0, 0, 1), QO(2, 0, 0)}, {QO(1, 0, 1), QO(2, 0, 0)}, {QO(3, 0, 0), QO(1, 0, 1)}, {QO(1, 0, 1), QO(2, 1, 0)},
 };
 #undef QO
-
-// Exp-Golomb length of se(v) with a count-leading-zeros instead of a loop
-__device__ __forceinline__ int mvbits(int v) {
-  uint32_t x = (v <= 0 ? static_cast<uint32_t>(-2 * v) : static_cast<uint32_t>(2 * v - 1)) + 1u;
-  return 2 * (31 - __clz(x)) + 1;
-}
-
-// per-byte rounding average (a + b + 1) >> 1 of two packed words
-__device__ __forceinline__ uint32_t avg4(uint32_t a, uint32_t b) {
-  return (a | b) - (((a ^ b) >> 1) & 0x7F7F7F7Fu);
-}
 
 __device__ __forceinline__ int wave_min_key(int key) { return min64(key); }
 __device__ __forceinline__ int wave_sum(int v) { return sum64(v); }
@@ -221,7 +207,7 @@ __device__ __forceinline__ int int_search_fixed(const SH& S, int sh0, int lane, 
   for (int j = 0; j < DYN; ++j) {
     const int dy = dy0 + j;
     const int mvx = (cx + dx - R) * 4, mvy = (cy + dy - R) * 4;
-    const int cost = static_cast<int>(acc[j]) + lambda * (mvbits(mvx - pmx) + mvbits(mvy - pmy));
+    const int cost = static_cast<int>(acc[j]) + lambda * (mvbits_se(mvx - pmx) + mvbits_se(mvy - pmy));
     const int key = (g < G && dy < side) ? ((cost << 12) | (dy * side + dx)) : 0x7FFFFFFF;
     best = key < best ? key : best;
   }
@@ -229,7 +215,7 @@ __device__ __forceinline__ int int_search_fixed(const SH& S, int sh0, int lane, 
 }
 
 // Frame-level half-sample planes of a reference batch (clause 8.4.2.2.1): for every
-// integer position (x, y) of a (W + 8) x (H + 8) grid (margin kHpM, coordinates of the
+// integer position (x, y) of a (W + 8) x (H + 8) grid (margin kHpMargin, coordinates of the
 // reference clamped to the picture = the normative edge extension):
 //   b = half between x and x+1, h = half between y and y+1, j = centre.
 // Values outside the margin equal the margin's (all 6 taps replicate), so a consumer
@@ -260,14 +246,14 @@ __device__ __forceinline__ void hp_load_row(const uint8_t* fr, int W, int H, int
 // into the pools [B, nbuf, plane]
 __global__ __launch_bounds__(256) void me_halfpel_planes(const uint8_t* __restrict__ ref, int W, int H,
                                                          uint8_t* __restrict__ hp, const SlotRoute* rt, int nbuf) {
-  const int PW = W + 2 * kHpM, PH = H + 2 * kHpM;
+  const int PW = W + 2 * kHpMargin, PH = H + 2 * kHpMargin;
   const int q = blockIdx.x * 64 + (threadIdx.x & 63);
   const int py0 = (blockIdx.y * 4 + (threadIdx.x >> 6)) * kHpRows;
   if (q >= PW / 4 || py0 >= PH) return;
   const int slot = blockIdx.z;
   if (rt && (rt[slot].kind < 0 || !(rt[slot].flags & SF_REF))) return;
   const size_t pslot = route_index(rt, nbuf, slot, RO_CUR);
-  const int x0 = 4 * q - kHpM, y0 = py0 - kHpM;
+  const int x0 = 4 * q - kHpMargin, y0 = py0 - kHpMargin;
   const uint8_t* fr = ref + pslot * W * H;
   const bool xin = x0 - 4 >= 0 && x0 + 8 <= W;
   // window: source rows y-2 .. y+3 (p) and their horizontal 6-tap sums (b1)
@@ -492,7 +478,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     for (int k = 0; k < 6; ++k) {
       if (k >= ncand) break;
       int sad = csad[k];
-      int cost = sad + lambda * (mvbits(cand_x[k] * 4 - pmx) + mvbits(cand_y[k] * 4 - pmy));
+      int cost = sad + lambda * (mvbits_se(cand_x[k] * 4 - pmx) + mvbits_se(cand_y[k] * 4 - pmy));
       if (cost < best) {
         best = cost;
         cx = cand_x[k];
@@ -546,7 +532,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         sad = sad4(sv.w, __builtin_amdgcn_alignbyte(a4, a3, sh), sad);
       }
       int mvx = (cx + dx - R) * 4, mvy = (cy + dy - R) * 4;
-      int cost = static_cast<int>(sad) + lambda * (mvbits(mvx - pmx) + mvbits(mvy - pmy));
+      int cost = static_cast<int>(sad) + lambda * (mvbits_se(mvx - pmx) + mvbits_se(mvy - pmy));
       int key = (cost << 12) | p;
       best_key = key < best_key ? key : best_key;
     }
@@ -556,7 +542,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
   if (zero_outside) {
     int sad = wave_sum(static_cast<int>(sad4(my_src, *reinterpret_cast<const uint32_t*>(
                                                           ref + static_cast<size_t>(Y0 + r4) * W + X0 + c4), 0)));
-    int cost = sad + lambda * (mvbits(-pmx) + mvbits(-pmy));
+    int cost = sad + lambda * (mvbits_se(-pmx) + mvbits_se(-pmy));
     int key = (cost << 12) | 4095;
     best_key = key < best_key ? key : best_key;
   }
@@ -579,13 +565,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
   // picture by me_halfpel_planes (the per-MB 6-tap filtering they replace was ~20% of
   // this kernel's instructions).  P(u, v) = plane at (X0+bx-2+u, Y0+by-2+v).
   {
-    const int PW = W + 2 * kHpM, PH = H + 2 * kHpM;
+    const int PW = W + 2 * kHpMargin, PH = H + 2 * kHpMargin;
     const uint8_t* hp = a.hp + rslot * 3 * PW * PH;
     const int x0 = X0 + bx - 2, y0 = Y0 + by - 2;  // frame coordinates of P(0, 0)
     // aligned words covering bytes x0 .. x0 + 19 of every row: 6 per row from xa = x0 & ~3
     const int xa = x0 & ~3;
     const bool gin = xa >= 0 && xa + kPP <= W;                      // reference row, no clamping
-    const bool xin = xa + kHpM >= 0 && xa + kHpM + kPP <= PW;       // half-sample plane row
+    const bool xin = xa + kHpMargin >= 0 && xa + kHpMargin + kPP <= PW;       // half-sample plane row
     // 4 planes (G from the reference itself, b / h / j from hp) x 20 rows x 6 words =
     // 480 words, one batch of loads; lane item i -> (plane, row, word)
     uint32_t v[8];
@@ -604,14 +590,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
             for (int q = 0; q < 4; ++q) word |= static_cast<uint32_t>(row[clampi(xa + 4 * w + q, 0, W - 1)]) << (8 * q);
           }
         } else {
-          const int yy = clampi(y0 + r, -kHpM, H + kHpM - 1) + kHpM;
+          const int yy = clampi(y0 + r, -kHpMargin, H + kHpMargin - 1) + kHpMargin;
           const uint8_t* row = hp + static_cast<size_t>(pl - 1) * PW * PH + static_cast<size_t>(yy) * PW;
           if (xin) {
-            word = *reinterpret_cast<const uint32_t*>(row + xa + kHpM + 4 * w);
+            word = *reinterpret_cast<const uint32_t*>(row + xa + kHpMargin + 4 * w);
           } else {
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-              word |= static_cast<uint32_t>(row[clampi(xa + 4 * w + q, -kHpM, W + kHpM - 1) + kHpM]) << (8 * q);
+              word |= static_cast<uint32_t>(row[clampi(xa + 4 * w + q, -kHpMargin, W + kHpMargin - 1) + kHpMargin]) << (8 * q);
           }
         }
       }
@@ -637,7 +623,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
   // 4 predicted samples of a row starting at plane coords (u, v) (G(u,v) = pixel (bx-2+u, by-2+v))
   auto pred4 = [&](int u, int v, int offa, int offb) -> uint32_t {
     const int base = v * kPP + u + psh;
-    return avg4(load4(base + offa), load4(base + offb));
+    return avg4b(load4(base + offa), load4(base + offb));
   };
   // ---- sub-sample SATD on MFMA.  One v_mfma_f32_16x16x16_f16 evaluates one 4x4-block row
   // (blocks (b, t), b = 0..3) of 4 candidates: output column n = lane & 15 = (candidate
@@ -692,7 +678,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
       ring(c, 2, &ox, &oy);
       int s = satd_cand(ox, oy);
       int mvx = best_mvx + ox, mvy = best_mvy + oy;
-      int cost = s + lambda * (mvbits(mvx - pmx) + mvbits(mvy - pmy));
+      int cost = s + lambda * (mvbits_se(mvx - pmx) + mvbits_se(mvy - pmy));
       int key = ci < ncand_h ? ((cost << 4) | c) : 0x7FFFFFFF;
       bkey = key < bkey ? key : bkey;
     }
@@ -708,7 +694,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         ring(ci, 1, &ox, &oy);
         int s = satd_cand(hx + ox, hy + oy);
         int mvx = best_mvx + hx + ox, mvy = best_mvy + hy + oy;
-        int cost = s + lambda * (mvbits(mvx - pmx) + mvbits(mvy - pmy));
+        int cost = s + lambda * (mvbits_se(mvx - pmx) + mvbits_se(mvy - pmy));
         int key = (cost << 4) | ci;
         qkey = key < qkey ? key : qkey;
       }
@@ -816,7 +802,7 @@ using namespace mivc::gpu;
 // b / h / j planes of B reference pictures into hp ([B, 3, H + 8, W + 8], margin 4)
 extern "C" void mivc_launch_me_halfpel(int B, int W, int H, const uint8_t* ref_y, uint8_t* hp, void* stream,
                                        const void* route, int nbuf) {
-  const int PW = W + 2 * kHpM, PH = H + 2 * kHpM;
+  const int PW = W + 2 * kHpMargin, PH = H + 2 * kHpMargin;
   const dim3 grid((PW / 4 + 63) / 64, (PH + 4 * kHpRows - 1) / (4 * kHpRows), B);
   hipLaunchKernelGGL(me_halfpel_planes, grid, dim3(256), 0, static_cast<hipStream_t>(stream), ref_y, W, H, hp,
                      static_cast<const SlotRoute*>(route), nbuf);
@@ -836,7 +822,7 @@ extern "C" void mivc_launch_me(int B, int wmb, int hmb, const uint8_t* src_y, co
   const int W = wmb * 16, H = hmb * 16;
   uint8_t* hp = hp_buf;
   if (!hp) {
-    const size_t hp_bytes = static_cast<size_t>(B) * 3 * (W + 2 * kHpM) * (H + 2 * kHpM) + 64;
+    const size_t hp_bytes = static_cast<size_t>(B) * 3 * (W + 2 * kHpMargin) * (H + 2 * kHpMargin) + 64;
     keep_async_pool();
     if (hipMallocAsync(reinterpret_cast<void**>(&hp), hp_bytes, s) != hipSuccess) {
       fprintf(stderr, "mivc_launch_me: hipMallocAsync(%zu) failed\n", hp_bytes);

@@ -117,7 +117,7 @@ class H264Params:
     # integer search radius of the two B-picture searches (their predictors are the scaled
     # co-located vectors of temporal direct, so a small window suffices)
     b_me_range: int = 4
-    # Jacobi passes of the P_Skip-aware vector choice after ME (csrc/kernels/bframe.hip
+    # Jacobi passes of the P_Skip-aware vector choice after ME (csrc/kernels/h264_p_refine.hip
     # p_mv_refine): 0 disables.  Each pass settles the field one MB further: 2 -> 4 passes is
     # -2.55 % BD-rate on the content suite for -1.3 % headline fps (profiles/r4_knob_sweep.md)
     skip_refine: int = 4
@@ -159,7 +159,7 @@ class H264Params:
     trellis: int = 2
     # x264 --direct: "temporal" (co-located motion scaled by POC distances: every MB decides in
     # parallel) or "spatial" (the neighbours' motion: b_decide keeps each searched MB's best
-    # explicit candidate, then bframe.hip b_spatial_decide derives the exact spatial motion in
+    # explicit candidate, then h264_b.hip b_spatial_decide derives the exact spatial motion in
     # an MB wavefront and takes direct where its SATD + lambda is not dearer; RD in
     # profiles/r3_direct_rd.md)
     direct: str = "temporal"

@@ -72,7 +72,7 @@ class HevcParams:
     cutree: bool = True
 
     # merge-aware vector choice after the search (Jacobi passes over the spatial merge
-    # neighbours' vectors, bframe.hip hevc_merge_refine); 0 disables
+    # neighbours' vectors, hevc_merge.hip hevc_merge_refine); 0 disables
     merge_refine: int = 4  # 1080p sweep (tools/hevc_knob_sweep.py): 0 -> 2 -> 4 passes = 3584 -> 3092 -> 3042 kb/s
     # x265 --signhide: the quantiser hides one sign per 4x4 group in the parity of the group's
     # levels (sign_data_hiding_enabled_flag).  Measured on the synthetic 1080p bench content:
@@ -120,7 +120,7 @@ class HevcParams:
     # x265 --tmvp (default on): temporal merge / AMVP candidates from the collocated anchor
     tmvp: bool = True
     # merge passes offer each 16x16 block the writer's exact merge list for a 16x16 CU
-    # (bframe.hip hevc_b_merge; P and B pictures); False: P pictures use the neighbour-vector
+    # (hevc_merge.hip hevc_b_merge; P and B pictures); False: P pictures use the neighbour-vector
     # approximation of round 2 (hevc_merge_refine)
     merge_exact: bool = True
     # merge passes after the first re-evaluate only blocks next to a block the previous pass
@@ -376,7 +376,7 @@ class GpuHevcEncoder:
     def _chg_args(self, it: int) -> tuple[int, int]:
         """(chg_in, chg_out) of merge pass ``it``: the first pass evaluates every block and
         records which moved; later passes re-evaluate only blocks next to a moved one
-        (bframe.hip hevc_b_merge -- the skipped blocks would reach the same decision)."""
+        (hevc_merge.hip hevc_b_merge -- the skipped blocks would reach the same decision)."""
         if not self.p.merge_skip:
             return 0, 0
         if getattr(self, "_chg", None) is None:

@@ -228,7 +228,7 @@ def test_me_halfpel_planes_match_numpy(W, H):
 
 
 def _refine_ref(src, planes, mv_in, cost, pm, pred, qps, lam_tab, wmb, hmb):
-    """One Jacobi pass of the P_Skip-aware vector choice (bframe.hip p_mv_refine) in numpy:
+    """One Jacobi pass of the P_Skip-aware vector choice (h264_p_refine.hip p_mv_refine) in numpy:
     each MB is offered the P_Skip predictor of its neighbours' current vectors (8.4.1.1) and
     takes it when SATD <= its own SATD + lambda * (mvd bits vs that predictor + 1)."""
     B = src.shape[0]

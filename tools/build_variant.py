@@ -3,7 +3,7 @@
 ``csrc/`` for same-box A/B timing: bench.py loads it through ``MIVC_HIP_LIB`` (with
 ``--allow-knobs``), so two variants run back to back on one GPU box.
 
-    python tools/build_variant.py NAME 'kernels/bframe.hip:s/old/new/' [more edits ...]
+    python tools/build_variant.py NAME 'kernels/h264_b.hip:s/old/new/' [more edits ...]
     python tools/build_variant.py NAME --patch my.diff
 
 Each edit is ``FILE:s/REGEX/REPLACEMENT/`` (Python ``re``, applied once per match,

@@ -1,18 +1,22 @@
 #!/usr/bin/env python3
-"""Record the golden bitstream hashes of tests/test_gpu_inter_layout.py.
+"""Record the golden bitstream hashes of tests/test_gpu_inter_layout.py (suite ``inter``) and
+tests/test_gpu_decide_layout.py (suite ``decide``).
 
-The test pins the bytes of small encodes, at shapes where the lane layout of encode_inter_mb
-can go wrong, to what the *parent* build of the kernels emits.  So this recorder never runs on
-the kernels under test: it needs MIVC_HIP_LIB to name a kernel library built from the parent
+The tests pin the bytes of small encodes, at shapes where the four-MBs-per-wave lane layout can
+go wrong, to what the *parent* build of the kernels emits.  So this recorder never runs on the
+kernels under test: it needs MIVC_HIP_LIB to name a kernel library built from the parent
 commit, e.g.
 
     python tools/build_variant.py parent --rev HEAD~1
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py tests/golden/inter_layout_parent.json
+    MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py decide tests/golden/decide_layout_parent.json
 
-The file holds, per case, the arguments (size, frames, clip seed / class, H264Params overrides)
-and the SHA-256 of every slot's bitstream.  Per case it also prints what the test asserts from
-the decoded records (split partitions, waves of four MBs mixing intra and inter MBs, waves
-mixing MBs with and without the 8x8 transform), so a case that would pass vacuously shows here.
+The file holds, per case, the arguments (size, frames, clip seed / class, parameter overrides)
+and the SHA-256 of every slot's bitstream.  Per case it also prints what the test asserts
+(``inter``: split partitions, waves of four MBs mixing intra and inter MBs, waves mixing MBs
+with and without the 8x8 transform; ``decide``: merge / skip CUs and bi-predicted CUs of the HEVC
+merge passes, B_Direct / B_Skip MBs of H.264 spatial direct), so a case that would pass
+vacuously shows here.
 """
 from __future__ import annotations
 
@@ -51,6 +55,41 @@ CASES = [
          params=dict(crf=None, qp=26, t8x8=True, trellis=2, aq_strength=1.0, refs=3, weightp=True, **_B3)),
     dict(id="176x144-b-noise-lowqp", width=176, height=144, frames=9, seed=11, kind="noise",
          params=dict(crf=None, qp=16, t8x8=True, trellis=2, aq_strength=1.0, **_B3)),
+]
+
+# The decision kernels that no other golden reaches: the HEVC merge passes (hevc_b_init_p /
+# hevc_b_merge, hevc_merge_refine, hevc_b_choose) and H.264 spatial direct (b_spatial_exact /
+# b_spatial_fixup, b_spatial_decide).  HEVC sizes are padded to the CTB, so a wave is always
+# full; what can go wrong is a wave straddling rows of 16x16 blocks (6 and 10 blocks per row)
+# and the z-scan availability at CTU edges (32x32 CTBs and 64x64 CTUs).  merge_exact=False
+# needs refs=1 (the neighbour-vector approximation carries no refIdx).
+_HQ = dict(crf=None, qp=30)
+_SP = dict(crf=None, qp=26, bframes=3, direct="spatial")
+DECIDE_CASES = [
+    dict(id="hevc-96x64-p-exact", codec="hevc", width=96, height=64, frames=6, seed=3, kind="default",
+         params=dict(bframes=0, merge_exact=True, ctu64=False, **_HQ)),
+    dict(id="hevc-96x64-p-refine", codec="hevc", width=96, height=64, frames=6, seed=4, kind="default",
+         params=dict(bframes=0, merge_exact=False, refs=1, ctu64=False, **_HQ)),
+    dict(id="hevc-96x64-b-tmvp", codec="hevc", width=96, height=64, frames=7, seed=5, kind="default",
+         params=dict(bframes=1, tmvp=True, ctu64=False, **_HQ)),
+    dict(id="hevc-160x96-b-tmvp", codec="hevc", width=160, height=96, frames=7, seed=6, kind="default",
+         params=dict(bframes=1, tmvp=True, ctu64=False, **_HQ)),
+    dict(id="hevc-160x96-p-refs3", codec="hevc", width=160, height=96, frames=8, seed=7, kind="default",
+         params=dict(bframes=0, merge_exact=True, refs=3, ref_gate=0, ctu64=False, **_HQ)),
+    dict(id="hevc-192x128-p-exact-ctu64", codec="hevc", width=192, height=128, frames=6, seed=8, kind="default",
+         params=dict(bframes=0, merge_exact=True, ctu64=True, **_HQ)),
+    dict(id="hevc-192x128-p-refine-ctu64", codec="hevc", width=192, height=128, frames=6, seed=9, kind="default",
+         params=dict(bframes=0, merge_exact=False, refs=1, ctu64=True, **_HQ)),
+    dict(id="hevc-192x128-b-tmvp-ctu64", codec="hevc", width=192, height=128, frames=7, seed=10, kind="default",
+         params=dict(bframes=1, tmvp=True, ctu64=True, **_HQ)),
+    dict(id="h264-80x48-spatial-fast", codec="h264", width=80, height=48, frames=9, seed=11, kind="default",
+         params=dict(**_SP)),
+    dict(id="h264-80x48-spatial-wavefront", codec="h264", width=80, height=48, frames=9, seed=12, kind="default",
+         params=dict(spatial_wavefront=True, **_SP)),
+    dict(id="h264-176x144-spatial-fast-pyramid", codec="h264", width=176, height=144, frames=9, seed=13,
+         kind="default", params=dict(pyramid=True, **_SP)),
+    dict(id="h264-176x144-spatial-wavefront", codec="h264", width=176, height=144, frames=9, seed=14,
+         kind="default", params=dict(spatial_wavefront=True, **_SP)),
 ]
 
 INTRA_KINDS = (0, 1, 4, 8)
@@ -93,7 +132,46 @@ def record_stats(host, bitstreams):
     return out
 
 
+def encode_decide_case(case):
+    """-> (encoder, results); the caller closes the encoder.  HEVC cases run the host entropy
+    writer with its CU counters on."""
+    import torch
+    from govideocompressor_amd.models.h264_gpu import synth_clip
+
+    if case["codec"] == "h264":
+        return encode_case(case)
+    from govideocompressor_amd.models.hevc_gpu import GpuHevcEncoder, HevcParams
+
+    p = HevcParams(width=case["width"], height=case["height"], **case["params"])
+    enc = GpuHevcEncoder(p, slots=SLOTS, entropy="host")
+    enc.cu_stats = {}
+    y, u, v = synth_clip(SLOTS, case["frames"], case["width"], case["height"], seed=case["seed"], kind=case["kind"])
+    res = enc.encode(y, u, v, keep_recon=True)
+    torch.cuda.synchronize()
+    return enc, res
+
+
+def decide_stats(host, case, enc, bitstreams):
+    """HEVC: merge + skip CUs of the P / B pictures (the writer's counters) and bi-predicted CUs
+    (decoded records).  H.264: B_Direct_16x16 / B_Skip MBs (decoded records)."""
+    import numpy as np
+
+    if case["codec"] == "h264":
+        direct = sum(int((np.asarray(seg["hdr"])[:, :, 0] == 13).sum()) for seg in host.parse(list(bitstreams), 1))
+        return dict(direct=direct)
+    merge = sum(int(st.get("merge_cus", 0)) + int(st.get("skip_cus", 0)) for k, st in enc.cu_stats.items() if k != "I")
+    bi = 0
+    for s in bitstreams:
+        for p in host.hevc_decode(s):
+            cu = p["cu"]
+            bi += int(((cu[:, 0] == 1) & (cu[:, 12] == 3)).sum())
+    return dict(merge=merge, bi=bi)
+
+
 def main() -> None:
+    suite = "inter"
+    if len(sys.argv) == 3 and sys.argv[1] in ("inter", "decide"):
+        suite = sys.argv.pop(1)
     if len(sys.argv) != 2:
         raise SystemExit(__doc__)
     lib = os.environ.get("MIVC_HIP_LIB")
@@ -103,11 +181,19 @@ def main() -> None:
 
     host = native.host()
     rows = []
-    for case in CASES:
-        enc, res = encode_case(case)
+    for case in (CASES if suite == "inter" else DECIDE_CASES):
+        if suite == "inter":
+            enc, res = encode_case(case)
+        else:
+            try:
+                enc, res = encode_decide_case(case)
+            except Exception as e:  # noqa: BLE001  the parent rejects the combination: not recorded
+                print(case["id"], "DROPPED:", repr(e), flush=True)
+                continue
         streams = [bytes(r.bitstream) for r in res]
+        stats = record_stats(host, streams) if suite == "inter" else decide_stats(host, case, enc, streams)
         enc.close()
-        print(case["id"], [len(s) for s in streams], record_stats(host, streams), flush=True)
+        print(case["id"], [len(s) for s in streams], stats, flush=True)
         rows.append(dict(case, sha256=[hashlib.sha256(s).hexdigest() for s in streams]))
     with open(sys.argv[1], "w") as f:
         json.dump(dict(slots=SLOTS, cases=rows), f, indent=1)
