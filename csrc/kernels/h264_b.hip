@@ -354,11 +354,35 @@ __global__ __launch_bounds__(64) void b_decide(BDecideArgs a) {
   const bool donly = (K == 1 || K == 3) ? true : (K == 2 ? false : static_cast<bool>(a.direct_only));
   const bool have_direct = K == 2 ? true : ((K == 1 || K == 3) ? false : static_cast<bool>(a.have_direct));
   const bool sfast = a.spatial == 2;
+  MbHeader* hrec = a.hdr + o;
+  uint32_t drw = 0;  // refIdxL0 of the four temporal-direct quadrants (bytes)
+  if (a.dref) drw = *reinterpret_cast<const uint32_t*>(a.dref + o * 4);
+  // gated MB (the search left kNoCost): B_Direct_16x16 with the pre-pass's prediction and cost
+  auto direct_record = [&]() {
+    if (lane == 0) {
+      hrec->kind = h264::MBK_BDIRECT;
+      hrec->sub_direct = 0;
+      if (!sfast) {  // (spatial: the estimate is in the record already)
+        *reinterpret_cast<uint2*>(&hrec->ref[0][0]) = make_uint2(drw, 0u);
+        uint4* mvp = reinterpret_cast<uint4*>(&hrec->mv[0][0][0]);
+        const uint4* dv = reinterpret_cast<const uint4*>(dm);  // [list][quadrant][xy] int16
+        mvp[0] = dv[0];
+        mvp[1] = dv[1];
+      }
+    }
+  };
+  if constexpr (K == 2) {
+    // nearly every MB of the main pass is gated: find that out before the vectors and the
+    // source rows are loaded for nothing
+    if (!(a.cost0[o] < kNoCost && a.cost1[o] < kNoCost)) {
+      direct_record();
+      return;
+    }
+  }
   const int m0x = donly ? 0 : a.mv0[o * 2], m0y = donly ? 0 : a.mv0[o * 2 + 1];
   const int m1x = donly ? 0 : a.mv1[o * 2], m1y = donly ? 0 : a.mv1[o * 2 + 1];
   uint32_t src[4];
   load_src4(g, r, a.src_y, src);
-  MbHeader* hrec = a.hdr + o;
   // The direct candidate per quadrant and list: refIdx (-1: list unused) and vector.
   //   temporal: the co-located block's scaled motion (b_direct_mv), list 1 from RefPicList1[0];
   //   spatial (fast, spatial == 2): the pre-pass estimates 8.4.1.2.2 from the neighbours'
@@ -366,8 +390,6 @@ __global__ __launch_bounds__(64) void b_decide(BDecideArgs a) {
   //     leaves it in the record; the main pass prices it; b_spatial_exact later derives the
   //     exact motion in decoding order and b_spatial_fixup re-predicts where it differs.
   int dref_[2][4], dvx[2][4], dvy[2][4];
-  uint32_t drw = 0;  // refIdxL0 of the four temporal-direct quadrants (bytes)
-  if (a.dref) drw = *reinterpret_cast<const uint32_t*>(a.dref + o * 4);
   if (K == 2 || K == 3) {
     // the lean passes: nothing here (each lane reads its own quadrant's direct motion, lane 0
     // re-reads it for the record)
@@ -432,21 +454,10 @@ __global__ __launch_bounds__(64) void b_decide(BDecideArgs a) {
       dvy[1][qq] = static_cast<int16_t>(w1_[qq] >> 16);
     }
   }
-  const bool searched = !donly && a.cost0[o] < kNoCost && a.cost1[o] < kNoCost;
+  const bool searched = K == 2 ? true : (!donly && a.cost0[o] < kNoCost && a.cost1[o] < kNoCost);
   uint8_t* pout = a.pred_out + o * 256 + by4 * 16 + bx4;   // row y at pout + 16 * y
   if (!donly && !searched && have_direct) {
-    // gated MB: B_Direct_16x16 with the pre-pass's prediction and cost
-    if (lane == 0) {
-      hrec->kind = h264::MBK_BDIRECT;
-      hrec->sub_direct = 0;
-      if (!sfast) {  // (spatial: the estimate is in the record already)
-        *reinterpret_cast<uint2*>(&hrec->ref[0][0]) = make_uint2(drw, 0u);
-        uint4* mvp = reinterpret_cast<uint4*>(&hrec->mv[0][0][0]);
-        const uint4* dv = reinterpret_cast<const uint4*>(dm);  // [list][quadrant][xy] int16
-        mvp[0] = dv[0];
-        mvp[1] = dv[1];
-      }
-    }
+    direct_record();
     return;
   }
   if constexpr (K == 2) {

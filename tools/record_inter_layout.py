@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Record the golden bitstream hashes of tests/test_gpu_inter_layout.py (suite ``inter``) and
-tests/test_gpu_decide_layout.py (suite ``decide``).
+"""Record the golden bitstream hashes of tests/test_gpu_inter_layout.py (suite ``inter``),
+tests/test_gpu_decide_layout.py (suite ``decide``) and tests/test_gpu_gate_layout.py (suite ``gate``).
 
 The tests pin the bytes of small encodes, at shapes where the four-MBs-per-wave lane layout can
 go wrong, to what the *parent* build of the kernels emits.  So this recorder never runs on the
@@ -10,13 +10,15 @@ commit, e.g.
     python tools/build_variant.py parent --rev HEAD~1
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py tests/golden/inter_layout_parent.json
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py decide tests/golden/decide_layout_parent.json
+    MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py gate tests/golden/gate_layout_parent.json
 
 The file holds, per case, the arguments (size, frames, clip seed / class, parameter overrides)
 and the SHA-256 of every slot's bitstream.  Per case it also prints what the test asserts
 (``inter``: split partitions, waves of four MBs mixing intra and inter MBs, waves mixing MBs
 with and without the 8x8 transform; ``decide``: merge / skip CUs and bi-predicted CUs of the HEVC
-merge passes, B_Direct / B_Skip MBs of H.264 spatial direct), so a case that would pass
-vacuously shows here.
+merge passes, B_Direct / B_Skip MBs of H.264 spatial direct; ``gate``: MBs the search gate stopped
+and MBs it let through, in the B pictures' list searches and in the farther list-0 pictures'), so
+a case that would pass vacuously shows here.  The ``gate`` suite stores those counts in the file.
 """
 from __future__ import annotations
 
@@ -91,6 +93,31 @@ DECIDE_CASES = [
     dict(id="h264-176x144-spatial-wavefront", codec="h264", width=176, height=144, frames=9, seed=14,
          kind="default", params=dict(spatial_wavefront=True, **_SP)),
 ]
+
+# Gated motion searches (me.hip: one wave per run of MBs): the B pictures' two list searches
+# behind b_gate (temporal direct's cost; < 0: lambdas of the MB's QP, which AQ changes inside a
+# run; 0: no gate) and the farther list-0 pictures' behind ref_gate (0: a gate nothing passes).
+# 15 and 99 MBs per slot: one partial run, and runs that end inside the picture for every run
+# length up to 64.
+_G = dict(crf=None, bframes=3, weightb=False, aq_strength=0.0)
+GATE_CASES = [
+    dict(id="80x48-bgate2400", width=80, height=48, frames=9, seed=21, kind="default",
+         params=dict(qp=24, b_gate=2400, refs=1, **_G)),
+    dict(id="80x48-bgate-150-weightb-aq", width=80, height=48, frames=9, seed=22, kind="default",
+         params=dict(crf=None, qp=24, bframes=3, weightb=True, aq_strength=1.0, b_gate=-150, refs=1)),
+    dict(id="80x48-bgate0", width=80, height=48, frames=5, seed=23, kind="default",
+         params=dict(qp=26, b_gate=0, refs=1, **_G)),
+    dict(id="80x48-bgate2400-refs3-refgate3000", width=80, height=48, frames=9, seed=24, kind="default",
+         params=dict(qp=24, b_gate=2400, refs=3, ref_gate=3000, **_G)),
+    dict(id="176x144-bgate2400-refs3-refgate3000", width=176, height=144, frames=9, seed=25, kind="default",
+         params=dict(qp=26, b_gate=2400, refs=3, ref_gate=3000, **_G)),
+    dict(id="176x144-bgate-150-refs3-refgate0", width=176, height=144, frames=9, seed=26, kind="default",
+         params=dict(qp=26, b_gate=-150, refs=3, ref_gate=0, **_G)),
+    dict(id="176x144-bgate0-refs3-refgate3000", width=176, height=144, frames=7, seed=27, kind="default",
+         params=dict(qp=24, b_gate=0, refs=3, ref_gate=3000, **_G)),
+]
+GATE_SENTINEL = -12345
+NO_COST = 0x3FFFFFFF
 
 INTRA_KINDS = (0, 1, 4, 8)
 SPLIT_KINDS = (5, 6, 7, 10, 11, 12)
@@ -168,9 +195,64 @@ def decide_stats(host, case, enc, bitstreams):
     return dict(merge=merge, bi=bi)
 
 
+class _GateCounter:
+    """Stands in for the encoder's kernel module: counts, per gated ``me`` launch, the MBs the
+    gate stopped (cost kNoCost) and let through, from the encoder's own cost buffer.  The
+    buffer is prefilled with a sentinel so that slots the launch skips (another picture type, a
+    shorter list 0) are told apart; their rows are put back, so the encode is unchanged."""
+
+    def __init__(self, enc):
+        self._enc, self._hip = enc, enc.hip
+        self.counts = dict(b_gated=0, b_searched=0, far_gated=0, far_searched=0)
+
+    def __getattr__(self, name):
+        return getattr(self._hip, name)
+
+    def me(self, *a):
+        if len(a) <= 24 or not a[18]:  # (positional as h264_gpu.py calls it: 18 = gate_cost, 24 = want)
+            return self._hip.me(*a)
+        enc = self._enc
+        outs = [enc.me_cost] + ([enc.me_cost1] if hasattr(enc, "me_cost1") else [])
+        outs += [enc.xcost[k] for k in range(enc.xcost.shape[0])] if hasattr(enc, "xcost") else []
+        t = next(x for x in outs if x.data_ptr() == a[7])
+        keep = t.clone()
+        t.fill_(GATE_SENTINEL)
+        self._hip.me(*a)
+        live = (t != GATE_SENTINEL).any(dim=1)
+        key = "b" if a[24] == 1 else "far"
+        self.counts[key + "_gated"] += int((t[live] == NO_COST).sum())
+        self.counts[key + "_searched"] += int((t[live] < NO_COST).sum())
+        t[~live] = keep[~live]
+
+
+def encode_gate_case(case):
+    """-> (encoder, results, counts of _GateCounter); the caller closes the encoder."""
+    import torch
+    from govideocompressor_amd.models.h264_gpu import GpuH264Encoder, H264Params, synth_clip
+
+    p = H264Params(width=case["width"], height=case["height"], **case["params"])
+    enc = GpuH264Encoder(p, slots=SLOTS)
+    counter = _GateCounter(enc)
+    enc.hip = counter
+    y, u, v = synth_clip(SLOTS, case["frames"], case["width"], case["height"], seed=case["seed"], kind=case["kind"])
+    res = enc.encode(y, u, v, keep_recon=True)
+    torch.cuda.synchronize()
+    return enc, res, counter.counts
+
+
+def gate_expect(case):
+    """The counts that must be > 0 for the case to exercise both sides of its gates."""
+    keys = []
+    if case["params"]["b_gate"] != 0:
+        keys += ["b_gated", "b_searched"]
+    if case["params"].get("refs", 1) > 1 and case["params"].get("ref_gate", 0) > 0:
+        keys += ["far_gated", "far_searched"]
+    return keys
+
+
 def main() -> None:
     suite = "inter"
-    if len(sys.argv) == 3 and sys.argv[1] in ("inter", "decide"):
+    if len(sys.argv) == 3 and sys.argv[1] in ("inter", "decide", "gate"):
         suite = sys.argv.pop(1)
     if len(sys.argv) != 2:
         raise SystemExit(__doc__)
@@ -181,7 +263,15 @@ def main() -> None:
 
     host = native.host()
     rows = []
-    for case in (CASES if suite == "inter" else DECIDE_CASES):
+    if suite == "gate":
+        for case in GATE_CASES:
+            enc, res, counts = encode_gate_case(case)
+            streams = [bytes(r.bitstream) for r in res]
+            enc.close()
+            vac = [k for k in gate_expect(case) if counts[k] == 0]
+            print(case["id"], [len(s) for s in streams], counts, "VACUOUS: " + ",".join(vac) if vac else "", flush=True)
+            rows.append(dict(case, counts=counts, sha256=[hashlib.sha256(s).hexdigest() for s in streams]))
+    for case in ([] if suite == "gate" else CASES if suite == "inter" else DECIDE_CASES):
         if suite == "inter":
             enc, res = encode_case(case)
         else:
