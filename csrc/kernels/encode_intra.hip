@@ -6,8 +6,18 @@
 // ... and waits on the row above through an LDS progress counter (workgroup-scope
 // release/acquire -- see kcommon.h).  Grid = B slots.
 //
-// For P frames only MBs flagged by encode_inter (intra_flag) are coded here; the
-// others were reconstructed by encode_inter and only advance the row counter.
+// For P / B pictures only MBs flagged by encode_inter (intra_flag) are coded here; the others
+// were reconstructed by encode_inter before this file's kernels start.  A flagged MB depends on
+// a neighbour only when that neighbour is flagged too, so the launcher issues two launches:
+//   encode_intra_free       one wave per run of kFreeSpan MBs over the whole device: classes the
+//                           run's flagged MBs in place and codes the free ones (none of L / TL /
+//                           T / TR is flagged) and the row runs that start at one inside its
+//                           span (kIntraFree); the rest is kIntraChained;
+//   encode_intra_wavefront  the wavefront above over the chained MBs alone, waiting on the row
+//                           above only where one of TL / T / TR is chained as well.
+// MBs that two different waves of the first launch code never neighbour each other, so no wave
+// of it reads what another writes; the stream order between the two launches is the only
+// ordering across workgroups.
 #include "h264_trellis.h"
 #include "../common/h264_i4_taps.h"
 
@@ -20,6 +30,15 @@ namespace gpu {
 using h264::MbHeader;
 
 constexpr int kIntraWaves = 16;  // default workgroup width of encode_intra_wavefront (see below)
+
+// intra_flag values of a P / B picture's MBs.  Every flagged MB stays non-zero while
+// encode_intra_free rewrites it, so a neighbour test racing with the write reads the same answer.
+// kIntraFree: coded by encode_intra_free; kIntraChained: left to the wavefront.
+enum IntraClass : uint8_t { kIntraNone = 0, kIntraFlagged = 1, kIntraFree = 2, kIntraChained = 3 };
+// MBs per wave of encode_intra_free (profiles/intra_free_mbs.md)
+constexpr int kFreeSpan = 32;
+// encode_intra_free also codes runs along a row that start inside a wave's span (same note)
+constexpr bool kFreeRuns = true;
 
 #ifdef MIVC_INTRA_PROFILE
 __device__ unsigned long long g_intra_prof[16][16];  // [mb][phase] for slot 0, wave 0
@@ -39,8 +58,12 @@ struct IntraArgs {
   MbHeader* hdr;
   int16_t* coef;
   uint8_t* nz;
-  const uint8_t* intra_flag;  // null: every MB is intra (I frame)
-  const int* intra_count;     // [B] (P frames)
+  // null: every MB is intra (I frame).  P / B: encode_inter's flags (0 / 1) on entry,
+  // encode_intra_free rewrites every flagged MB's as its class (IntraClass, never 0)
+  uint8_t* intra_flag;
+  // [B] (P / B): flagged MBs on entry; encode_intra_free takes off the free MBs it coded, so
+  // the wavefront launch sees the chained count
+  int* intra_count;
   int* err;
   int use_i4x4;
   int use_i8x8;  // High profile: Intra8x8 trial (x264 --partitions i8x8, with --8x8dct)
@@ -772,21 +795,87 @@ __global__ __launch_bounds__(64 * NW) void encode_intra_wavefront(IntraArgs a) {
       }
       continue;
     }
-    // P frame: fetch the row's intra flags 64 at a time and visit only flagged MBs
-    const size_t rowo = static_cast<size_t>(slot) * g.nmb() + static_cast<size_t>(y) * g.wmb;
+    // P / B picture: fetch the row's classes 64 at a time and visit only the chained MBs (the
+    // inter and the free ones were final before this launch started); an MB waits on the row
+    // above only when one of its TL / T / TR neighbours is chained too
+    const uint8_t* rowf = a.intra_flag + static_cast<size_t>(slot) * g.nmb() + static_cast<size_t>(y) * g.wmb;
+    const bool top = top_in_slice(y, a.slice_rows);
     for (int x0 = 0; x0 < g.wmb; x0 += 64) {
       const int xl = x0 + lane;
-      unsigned long long mask = __ballot(xl < g.wmb && a.intra_flag[rowo + xl] != 0);
+      const bool mine = xl < g.wmb && rowf[xl] == kIntraChained;
+      bool above = false;
+      if (mine && top) {
+        const uint8_t* up = rowf - g.wmb + xl;
+        above = up[0] == kIntraChained || (xl > 0 && up[-1] == kIntraChained) ||
+                (xl < g.wmb - 1 && up[1] == kIntraChained);
+      }
+      unsigned long long mask = __ballot(mine);
+      const unsigned long long above_mask = __ballot(above);
       while (mask) {
-        const int x = x0 + __builtin_ctzll(mask);
+        const int bit = __builtin_ctzll(mask);
+        const int x = x0 + bit;
         mask &= mask - 1;
-        if (x > 0) publish(y, x);  // MBs before x in this row are final (inter)
-        if (top_in_slice(y, a.slice_rows)) wait(y - 1, min(x + 2, g.wmb));
+        if (x > 0) publish(y, x);  // MBs before x in this row are final
+        if ((above_mask >> bit) & 1) wait(y - 1, min(x + 2, g.wmb));
         encode_intra_mb(a, S, slot, x, y, tapw);
         publish(y, x + 1);
       }
     }
     publish(y, g.wmb);
+  }
+}
+
+// The free intra MBs of P / B pictures: grid (ceil(nmb / SPAN), B), one wave per workgroup.
+// Lane i classes MB mb0 + i of the slot (availability as in encode_intra_mb: picture edges and
+// top_in_slice; the top-right neighbour counts even without the I4x4 / I8x8 trial, the body
+// stages its samples either way), then the wave codes its MBs one after another, in raster
+// order.  With kFreeRuns the wave also takes an MB whose only intra neighbour is the left one
+// when it codes that one itself (a run along a row that starts inside the wave's span): such an
+// MB reads nothing another wave writes either, and no other wave takes an MB next to it.
+template <int SPAN>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void encode_intra_free(IntraArgs a) {
+  __shared__ IntraShared S;
+  const Geom& g = a.g;
+  const int slot = blockIdx.y;
+  if (!route_active(a.rt, slot, -1)) return;  // uniform per workgroup
+  if (a.intra_count[slot] == 0) return;
+  const int lane = lane_id();
+  const int nmb = g.nmb(), mb0 = blockIdx.x * SPAN, mb = mb0 + lane;
+  uint8_t* f = a.intra_flag + static_cast<size_t>(slot) * nmb;
+  const bool mine = lane < SPAN && mb < nmb && f[mb] != kIntraNone;
+  const unsigned long long intra = __ballot(mine);
+  if (intra == 0) return;
+  bool left = false, above = false;
+  if (mine) {
+    const int my = mb / g.wmb, mx = mb - my * g.wmb;
+    left = mx > 0 && f[mb - 1] != kIntraNone;
+    if (top_in_slice(my, a.slice_rows)) {
+      const uint8_t* up = f + mb - g.wmb;
+      above = up[0] != kIntraNone || (mx > 0 && up[-1] != kIntraNone) || (mx < g.wmb - 1 && up[1] != kIntraNone);
+    }
+  }
+  const unsigned long long linked = __ballot(mine && left && !above);  // lane i - 1 holds the left MB
+  unsigned long long mask = __ballot(mine && !left && !above);         // the free MBs
+  if (kFreeRuns)
+    for (unsigned long long more; (more = (mask << 1) & linked & ~mask) != 0;) mask |= more;
+  if (mine) f[mb] = (mask >> lane) & 1 ? kIntraFree : kIntraChained;
+  if (mask == 0) return;
+  if (lane == 0) {
+    S.saved_x = -2;  // the left edge in LDS is only ever the one of the MB this wave coded last
+    atomicSub(a.intra_count + slot, __builtin_popcountll(mask));
+  }
+  uint32_t tapw[4];
+  {
+    const int m = lane >> 2 < 9 ? lane >> 2 : 0, r = lane & 3;
+#pragma unroll
+    for (int x = 0; x < 4; ++x) tapw[x] = h264::kI4Taps[m][r * 4 + x];
+  }
+  wave_sync();
+  while (mask) {
+    const int i = mb0 + __builtin_ctzll(mask);
+    mask &= mask - 1;
+    const int my = i / g.wmb;
+    encode_intra_mb(a, S, slot, i - my * g.wmb, my, tapw);
   }
 }
 
@@ -848,8 +937,9 @@ extern "C" void mivc_launch_encode_intra(int B, int wmb, int hmb, const uint8_t*
   a.hdr = static_cast<MbHeader*>(hdr);
   a.coef = coef;
   a.nz = nz;
-  a.intra_flag = intra_flag;
-  a.intra_count = intra_count;
+  // P / B: the caller's flag map and counts are this launcher's to reclassify (see IntraArgs)
+  a.intra_flag = const_cast<uint8_t*>(intra_flag);
+  a.intra_count = const_cast<int*>(intra_count);
   a.err = err;
   a.use_i4x4 = use_i4x4;
   a.use_i8x8 = use_i8x8;
@@ -880,6 +970,11 @@ extern "C" void mivc_launch_encode_intra(int B, int wmb, int hmb, const uint8_t*
   if (K > 1)
     (void)hipMemsetAsync(gprog, 0, static_cast<size_t>(units) * kMaxRows * sizeof(int),
                          static_cast<hipStream_t>(stream));
+  if (intra_flag) {
+    const int nmb = wmb * hmb;
+    hipLaunchKernelGGL(encode_intra_free<kFreeSpan>, dim3((nmb + kFreeSpan - 1) / kFreeSpan, B), dim3(64), 0,
+                       static_cast<hipStream_t>(stream), a);
+  }
   if (nw == 16)
     hipLaunchKernelGGL(encode_intra_wavefront<16>, dim3(B * per * K), dim3(64 * 16), 0, static_cast<hipStream_t>(stream), a);
   else if (nw == 12)

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Record the golden bitstream hashes of tests/test_gpu_inter_layout.py (suite ``inter``),
-tests/test_gpu_decide_layout.py (suite ``decide``) and tests/test_gpu_gate_layout.py (suite ``gate``).
+tests/test_gpu_decide_layout.py (suite ``decide``), tests/test_gpu_gate_layout.py (suite ``gate``)
+and tests/test_gpu_intra_free.py (suite ``intra``: planted intra MBs of P / B pictures, with the
+counts of free and chained ones per case).
 
 The tests pin the bytes of small encodes, at shapes where the four-MBs-per-wave lane layout can
 go wrong, to what the *parent* build of the kernels emits.  So this recorder never runs on the
@@ -11,6 +13,7 @@ commit, e.g.
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py tests/golden/inter_layout_parent.json
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py decide tests/golden/decide_layout_parent.json
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py gate tests/golden/gate_layout_parent.json
+    MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py intra tests/golden/intra_free_parent.json
 
 The file holds, per case, the arguments (size, frames, clip seed / class, parameter overrides)
 and the SHA-256 of every slot's bitstream.  Per case it also prints what the test asserts
@@ -118,6 +121,65 @@ GATE_CASES = [
 ]
 GATE_SENTINEL = -12345
 NO_COST = 0x3FFFFFFF
+
+# Intra MBs of P / B pictures (encode_intra.hip: free MBs a wave per run, chained MBs in the
+# wavefront): see tests/test_gpu_intra_free.py, whose clip builders and classifier this suite
+# runs.  spots: per slot, (mx, my) of the MBs planted in display frame plant_t; pics: display
+# indices of the pictures whose intra MBs are counted (None: every picture with an inter MB);
+# need: the classes the case is there for; free_spots / chained_spots: what single MBs must be.
+_IP = dict(crf=None, qp=26, bframes=0)
+_ISO = [[0, 3], [10, 2], [4, 0], [5, 8], [2, 5], [4, 5], [8, 4], [8, 6], [9, 8]]
+_PAIRS = [[2, 1], [3, 1], [6, 1], [6, 2], [1, 4], [2, 5], [6, 5], [5, 6]]
+_G33 = [[x, y] for y in (1, 2, 3) for x in (1, 2, 3)]
+_LSHAPE = [[6, 4], [6, 5], [6, 6], [7, 6], [8, 6]]
+
+
+def _spots(id_, w, h, spots, need, params=None, **kw):
+    return dict(dict(id=id_, width=w, height=h, frames=2, seed=17, clip="spots", plant_t=1, spots=spots, pics=[1],
+                     need=need, params=dict(_IP, **(params or {}))), **kw)
+
+
+INTRA_CASES = [
+    # every picture edge, two in a row two columns apart, two in a column two rows apart, one in
+    # the last partial run (MB 96 of 99); only free MBs: the wavefront launch returns at once
+    _spots("176x144-isolated", 176, 144, [_ISO, _ISO], ["free"], free_only=True, free_spots=[_ISO, _ISO]),
+    # one chained MB through L, T, TL and TR alone
+    _spots("176x144-pairs", 176, 144, [_PAIRS, _PAIRS], ["free", "chained"],
+           free_spots=[[[2, 1], [6, 1], [1, 4], [6, 5]]] * 2, chained_spots=[[[3, 1], [6, 2], [2, 5], [5, 6]]] * 2),
+    _spots("176x144-tr-pair-i4x4", 176, 144, [[[6, 5], [5, 6]]] * 2, ["free", "chained"], params=dict(i4x4_in_p=True),
+           free_spots=[[[6, 5]]] * 2, chained_spots=[[[5, 6]]] * 2),
+    _spots("176x144-groups", 176, 144, [_G33 + _LSHAPE] * 2, ["free", "chained"],
+           free_spots=[[[1, 1], [6, 4]]] * 2, chained_spots=[[s for s in _G33 + _LSHAPE if s not in ([1, 1], [6, 4])]] * 2),
+    # 5 MBs per row, 15 MBs: one partial run; slot 0 codes MB 1 then MB 8, slot 1 MB 1 then MB 12
+    # (one column right of the previous one, two rows down)
+    _spots("80x48-straddle", 80, 48, [[[1, 0], [3, 1]], [[1, 0], [2, 2]]], ["free"], free_only=True,
+           free_spots=[[[1, 0], [3, 1]], [[1, 0], [2, 2]]]),
+    # 11 MBs per row: MBs 37 and 50 (and 32 and 45, inside one run of 16); slot 1: MBs 37 and 60
+    # (column + 1, two rows down) and MB 96 in the last partial run
+    _spots("176x144-straddle", 176, 144, [[[4, 3], [6, 4], [10, 2], [1, 4]], [[4, 3], [5, 5], [8, 8]]], ["free"],
+           free_only=True, free_spots=[[[4, 3], [6, 4], [10, 2], [1, 4]], [[4, 3], [5, 5], [8, 8]]]),
+    # row runs and the edges of a wave's span: MBs 31 | 32 (a pair across the edge of a span of 16
+    # or 32 MBs), MBs 65 and 66 (last of a row, first of the next: raster neighbours that are not
+    # neighbours); slot 1: a run of four over MBs 47 | 48
+    _spots("176x144-span-edge", 176, 144, [[[9, 2], [10, 2], [10, 5], [0, 6]], [[3, 4], [4, 4], [5, 4], [6, 4]]],
+           ["free", "chained"], free_spots=[[[9, 2], [10, 5], [0, 6]], [[3, 4]]],
+           chained_spots=[[[10, 2]], [[4, 4], [5, 4], [6, 4]]]),
+    # slot 0 without an intra MB: both launches return for it
+    _spots("176x144-empty-slot", 176, 144, [[], _G33 + _ISO[1:2] + [[8, 6], [9, 8], [7, 0]]], ["free", "chained"]),
+    dict(id="176x144-scenecut", width=176, height=144, frames=30, seed=2, clip="cut", cut=27, pics=[27],
+         need=["free", "chained"], params=dict()),
+    _spots("176x144-b-planted", 176, 144, [[[2, 2], [8, 6], [5, 4], [6, 4]]] * 2, ["free", "chained"],
+           params=dict(bframes=3, lookahead=False), frames=5, plant_t=2, pics=[2], b_picture=True,
+           free_spots=[[[2, 2], [8, 6], [5, 4]]] * 2, chained_spots=[[[6, 4]]] * 2),
+    # two slices of four MB rows: (5, 4) starts the second slice right under (5, 3)
+    _spots("176x128-slices2", 176, 128, [[[5, 3], [5, 4], [8, 1], [9, 1]]] * 2, ["free", "chained"], params=dict(slices=2),
+           free_spots=[[[5, 3], [5, 4], [8, 1]]] * 2, chained_spots=[[[9, 1]]] * 2),
+    # the two noisy cases of the inter suite, with their counts
+    dict(id="80x48-p-noise-lowqp", width=80, height=48, frames=6, seed=9, clip="synth", kind="noise", pics=None, need=[],
+         params=dict(crf=None, qp=18, t8x8=True, trellis=2, aq_strength=1.0, **_P)),
+    dict(id="176x144-b-noise-lowqp", width=176, height=144, frames=9, seed=11, clip="synth", kind="noise", pics=None,
+         need=["free", "chained"], params=dict(crf=None, qp=16, t8x8=True, trellis=2, aq_strength=1.0, **_B3)),
+]
 
 INTRA_KINDS = (0, 1, 4, 8)
 SPLIT_KINDS = (5, 6, 7, 10, 11, 12)
@@ -250,9 +312,54 @@ def gate_expect(case):
     return keys
 
 
+def record_intra(host, path) -> None:
+    """Suite ``intra``: per case the per-slot hashes and the free / chained intra MB counts of
+    the decoded P / B pictures.  The clips and the classifier are the test's own (the test
+    module reads the golden file when imported, so a first recording starts from an empty one)."""
+    import torch
+    from govideocompressor_amd.models.h264_gpu import GpuH264Encoder, H264Params
+
+    if not os.path.exists(path):
+        with open(path, "w") as f:
+            json.dump(dict(slots=SLOTS, cases=[]), f)
+    from tests import test_gpu_intra_free as T
+
+    rows = []
+    for case in INTRA_CASES:
+        case = json.loads(json.dumps(case))  # as the test will read it
+        enc = GpuH264Encoder(H264Params(width=case["width"], height=case["height"], **case["params"]), slots=SLOTS)
+        y, u, v = T._clip(case, SLOTS)
+        res = enc.encode(y, u, v, keep_recon=True)
+        torch.cuda.synchronize()
+        slice_rows = int(enc.slice_rows)
+        enc.close()
+        streams = [bytes(r.bitstream) for r in res]
+        counts, planted = T._counts(case, [host.decode(s) for s in streams], slice_rows)
+        vac = [k for k in case["need"] if counts[k] == 0]
+        for b, (kinds, intra, free, chained) in enumerate(planted):
+            vac += [f"slot {b} {s} not intra" for s in case["spots"][b] if not intra[s[1], s[0]]]
+            vac += [f"slot {b} {s} not free" for s in case.get("free_spots", [[], []])[b] if not free[s[1], s[0]]]
+            vac += [f"slot {b} {s} not chained" for s in case.get("chained_spots", [[], []])[b] if not chained[s[1], s[0]]]
+            if case.get("b_picture") and not np_isin_any(kinds, (9, 10, 11, 12, 13)):
+                vac.append(f"slot {b}: not a B picture")
+            if case.get("free_only") and chained.any():
+                vac.append(f"slot {b}: chained MBs")
+        print(case["id"], [len(s) for s in streams], counts, "VACUOUS: " + "; ".join(vac) if vac else "", flush=True)
+        rows.append(dict(case, counts=counts, sha256=[hashlib.sha256(s).hexdigest() for s in streams]))
+    with open(path, "w") as f:
+        json.dump(dict(slots=SLOTS, cases=rows), f, indent=1)
+        f.write("\n")
+
+
+def np_isin_any(a, values) -> bool:
+    import numpy as np
+
+    return bool(np.isin(a, values).any())
+
+
 def main() -> None:
     suite = "inter"
-    if len(sys.argv) == 3 and sys.argv[1] in ("inter", "decide", "gate"):
+    if len(sys.argv) == 3 and sys.argv[1] in ("inter", "decide", "gate", "intra"):
         suite = sys.argv.pop(1)
     if len(sys.argv) != 2:
         raise SystemExit(__doc__)
@@ -263,6 +370,9 @@ def main() -> None:
 
     host = native.host()
     rows = []
+    if suite == "intra":
+        record_intra(host, sys.argv[1])
+        return
     if suite == "gate":
         for case in GATE_CASES:
             enc, res, counts = encode_gate_case(case)
