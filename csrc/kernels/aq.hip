@@ -6,6 +6,9 @@
 //                     squared sum / n, x264 ac_energy_var), offset = round(strength * 1.0397 *
 //                     (log2(energy) - 14.427)), the x264 formula for 8-bit video.
 //                     (+ the MB-tree offset of the MB when given, mbtree.hip)
+//   prep_aq_rows      the same offsets written while the source picture is padded to the coded
+//                     size (frame_prep.hip's copy and h264_aq_offsets in one pass: the source
+//                     is read once instead of read, written and read again)
 //   h264_qp_flags     per MB: does it carry mb_qp_delta (coded residual, or Intra16x16)?
 //                     (luma from the encoder's non-zero flags, which hold for every MB kind
 //                     but Intra16x16, whose flag is set regardless)
@@ -21,6 +24,19 @@ namespace mivc {
 namespace gpu {
 
 using h264::MbHeader;
+
+// The offset of one MB from its sample sums and sums of squares (luma 256, Cb and Cr 64
+// samples each); `extra` (nullable): the MB-tree offset at extra[xi], added before rounding.
+__device__ __forceinline__ int8_t aq_offset(int s, int ss, int cb_s, int cb_ss, int cr_s, int cr_ss, float strength,
+                                            const float* extra, long long xi) {
+  // the squared luma sum exceeds INT_MAX once the MB mean passes 181: unsigned products
+  const uint32_t us = static_cast<uint32_t>(s);
+  const uint32_t e = (static_cast<uint32_t>(ss) - ((us * us) >> 8)) +
+                     static_cast<uint32_t>(cb_ss - ((cb_s * cb_s) >> 6)) + static_cast<uint32_t>(cr_ss - ((cr_s * cr_s) >> 6));
+  float adj = strength * 1.0397f * (log2f(static_cast<float>(e > 1u ? e : 1u)) - 14.427f);
+  if (extra) adj += extra[xi];  // MB-tree offset of this frame
+  return static_cast<int8_t>(clampi(static_cast<int>(rintf(adj)), -24, 24));
+}
 
 // 16 lanes per MB (4 MBs per wave, 16 per 256-thread workgroup): lane l of a group sums
 // luma row l (4 dwords) and, for l < 8 Cb row l / for l >= 8 Cr row l - 8 (2 dwords); the
@@ -74,30 +90,102 @@ __global__ __launch_bounds__(256) void h264_aq_offsets(Geom g, const uint8_t* __
   s = sum16(s);
   ss = sum16(ss);
   const int cr_s = __shfl(cb_s, (lane_id() & ~15) + 8, 64), cr_ss = __shfl(cb_ss, (lane_id() & ~15) + 8, 64);
-  if (live && l == 0) {
-    // the squared luma sum exceeds INT_MAX once the MB mean passes 181: unsigned products
-    const uint32_t us = static_cast<uint32_t>(s);
-    const uint32_t e = (static_cast<uint32_t>(ss) - ((us * us) >> 8)) +
-                       static_cast<uint32_t>(cb_ss - ((cb_s * cb_s) >> 6)) + static_cast<uint32_t>(cr_ss - ((cr_s * cr_s) >> 6));
-    float adj = strength * 1.0397f * (log2f(static_cast<float>(e > 1u ? e : 1u)) - 14.427f);
-    if (extra) adj += extra[slot * extra_stride + mb];  // MB-tree offset of this frame
-    out[static_cast<size_t>(slot) * nmb + mb] = static_cast<int8_t>(clampi(static_cast<int>(rintf(adj)), -24, 24));
+  if (live && l == 0)
+    out[static_cast<size_t>(slot) * nmb + mb] = aq_offset(s, ss, cb_s, cb_ss, cr_s, cr_ss, strength, extra, slot * extra_stride + mb);
   }
+}
+
+// Padding and adaptive quantisation in one pass over the source (the fast path of
+// mivc_launch_prep_aq: display width == coded width, 16-byte rows): a lane takes one MB
+// column, a wave the 16 luma and 2 x 8 chroma rows of up to 64 neighbouring MBs of an MB
+// row.  Every row is loaded once (rows past the display height from its last row), stored
+// to the coded-size planes and summed in place, so an MB's sums live in one lane.  All
+// loads of a plane are issued before its first store (16 x 16 bytes in flight per lane,
+// 1 KiB contiguous per wave and row).  Offsets: aq_offset, as h264_aq_offsets.
+constexpr int kPrepAqWaves = 4;  // MB-row units per workgroup
+
+__global__ __launch_bounds__(64 * kPrepAqWaves) void prep_aq_rows(
+    const uint8_t* __restrict__ in_y, const uint8_t* __restrict__ in_u, const uint8_t* __restrict__ in_v, int h,
+    int64_t in_stride_y, int64_t in_stride_c, const int* __restrict__ fsel, int64_t fstep_y, int64_t fstep_c, Geom g,
+    uint8_t* __restrict__ out_y, uint8_t* __restrict__ out_u, uint8_t* __restrict__ out_v, float strength,
+    const float* __restrict__ extra, long long extra_stride, int8_t* __restrict__ out, const SlotRoute* rt) {
+  const int slot = blockIdx.y;
+  const int groups = (g.wmb + 63) >> 6;  // 64-column groups of an MB row
+  const int unit = blockIdx.x * kPrepAqWaves + wave_id();
+  if (unit >= g.hmb * groups) return;  // (wave-uniform)
+  const int my = unit / groups, mx = (unit - my * groups) * 64 + lane_id();
+  if (mx >= g.wmb) return;  // no cross-lane step below
+  const int nmb = g.nmb(), mb = my * g.wmb + mx;
+  if (extra && rt) {  // as h264_aq_offsets
+    const SlotRoute& r = rt[slot];
+    extra = (r.kind >= 0 && r.disp >= 0 && (r.flags & SF_REF)) ? extra + static_cast<size_t>(r.disp) * nmb : nullptr;
   }
+  const int64_t f = fsel ? fsel[slot] : 0;
+  const int W = g.W, cw = g.cw(), hc = h >> 1;
+  uint32_t s = 0, ss = 0;
+  {
+    const uint8_t* src = in_y + slot * in_stride_y + f * fstep_y + mx * 16;
+    uint8_t* dst = out_y + slot * g.ysize() + static_cast<size_t>(my * 16) * W + mx * 16;
+    uint4 v[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) v[r] = *reinterpret_cast<const uint4*>(src + static_cast<size_t>(min(my * 16 + r, h - 1)) * W);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      *reinterpret_cast<uint4*>(dst + static_cast<size_t>(r) * W) = v[r];
+      const uint32_t w[4] = {v[r].x, v[r].y, v[r].z, v[r].w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        s = __builtin_amdgcn_udot4(w[k], 0x01010101u, s, false);
+        ss = __builtin_amdgcn_udot4(w[k], w[k], ss, false);
+      }
+    }
+  }
+  uint32_t cs[2] = {0, 0}, css[2] = {0, 0};
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const uint8_t* src = (c ? in_v : in_u) + slot * in_stride_c + f * fstep_c + mx * 8;
+    uint8_t* dst = (c ? out_v : out_u) + slot * g.csize() + static_cast<size_t>(my * 8) * cw + mx * 8;
+    uint2 v[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) v[r] = *reinterpret_cast<const uint2*>(src + static_cast<size_t>(min(my * 8 + r, hc - 1)) * cw);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      *reinterpret_cast<uint2*>(dst + static_cast<size_t>(r) * cw) = v[r];
+      cs[c] = __builtin_amdgcn_udot4(v[r].x, 0x01010101u, cs[c], false);
+      cs[c] = __builtin_amdgcn_udot4(v[r].y, 0x01010101u, cs[c], false);
+      css[c] = __builtin_amdgcn_udot4(v[r].x, v[r].x, css[c], false);
+      css[c] = __builtin_amdgcn_udot4(v[r].y, v[r].y, css[c], false);
+    }
+  }
+  out[static_cast<size_t>(slot) * nmb + mb] = aq_offset(static_cast<int>(s), static_cast<int>(ss), static_cast<int>(cs[0]),
+                                                        static_cast<int>(css[0]), static_cast<int>(cs[1]),
+                                                        static_cast<int>(css[1]), strength, extra, slot * extra_stride + mb);
 }
 
 // 16 lanes per MB (16 MBs per 256-thread workgroup).  The MB carries mb_qp_delta iff it
 // is Intra16x16 or has a non-zero level (coded_block_pattern != 0): luma from the encoder's
 // per-block non-zero flags (lane 9, 16 bytes), chroma AC from coefficient 1 (lanes 0..7),
 // chroma DC (lane 8), the MB kind (lane 10).
+// pre / rt (nullable, both or none): the byte encode_inter_mb left per MB of the slots that
+// code a P or B picture this step (0 / 1: the answer for an inter MB; 2: handed to the intra
+// kernels, which decide its levels later).  Only the route says whether a slot's bytes are of
+// this step; an MB with 2, the other slots and launches without `pre` read the levels.
 __global__ __launch_bounds__(256) void h264_qp_flags(Geom g, const MbHeader* __restrict__ hdr,
                                                      const int16_t* __restrict__ coef, const uint8_t* __restrict__ nzf,
-                                                     uint8_t* __restrict__ flags) {
+                                                     uint8_t* __restrict__ flags, const uint8_t* __restrict__ pre,
+                                                     const SlotRoute* rt) {
   const int lane = lane_id(), sub = lane & 15, grp = lane >> 4;
   const int nmb = g.nmb();
   const int mb = blockIdx.x * 16 + (threadIdx.x >> 4), slot = blockIdx.y;
   const bool live = mb < nmb;
   const size_t o = static_cast<size_t>(slot) * nmb + (live ? mb : 0);
+  if (pre && rt && live && (rt[slot].kind == SK_P || rt[slot].kind == SK_B)) {
+    const uint8_t p = pre[o];
+    if (p < 2) {  // the MB's whole 16-lane group leaves: the ballot below is read per group
+      if (sub == 0) flags[o] = p;
+      return;
+    }
+  }
   const int16_t* c = coef + o * h264::kCoefPerMb;
   bool nz = false;
   if (live && sub < 8) {
@@ -165,14 +253,39 @@ extern "C" void mivc_launch_aq_offsets(int B, int wmb, int hmb, const uint8_t* s
                      sy, su, sv, strength, extra, extra_stride, out, static_cast<const SlotRoute*>(route));
 }
 
+// Pad frame fsel[slot] (nullable: frame 0) of every slot's clip to the coded size and write its
+// AQ offsets in one launch.  Returns 0 and launches nothing unless the display width is the
+// coded width and every row chunk is aligned (16 bytes luma, 8 bytes chroma): the caller then
+// runs mivc_launch_prep and mivc_launch_aq_offsets.
+extern "C" int mivc_launch_prep_aq(const uint8_t* in_y, const uint8_t* in_u, const uint8_t* in_v, int w, int h,
+                                   int64_t in_stride_y, int64_t in_stride_c, int B, uint8_t* out_y, uint8_t* out_u,
+                                   uint8_t* out_v, int W, int H, const int* fsel, float strength, const float* extra,
+                                   long long extra_stride, int8_t* out, void* stream, const void* route) {
+  auto al = [](const void* p, uintptr_t n) { return reinterpret_cast<uintptr_t>(p) % n == 0; };
+  const int64_t fstep_y = static_cast<int64_t>(w) * h, fstep_c = static_cast<int64_t>(w / 2) * (h / 2);
+  const bool fast = w == W && W % 16 == 0 && H % 16 == 0 && h % 2 == 0 && h >= 2 && h <= H && strength > 0.f &&
+                    in_stride_y % 16 == 0 && in_stride_c % 8 == 0 && fstep_y % 16 == 0 && fstep_c % 8 == 0 &&
+                    al(in_y, 16) && al(in_u, 8) && al(in_v, 8) && al(out_y, 16) && al(out_u, 8) && al(out_v, 8);
+  if (!fast) return 0;
+  const Geom g{B, W / 16, H / 16, W, H};
+  const int units = g.hmb * ((g.wmb + 63) / 64);
+  hipLaunchKernelGGL(prep_aq_rows, dim3((units + kPrepAqWaves - 1) / kPrepAqWaves, B), dim3(64 * kPrepAqWaves), 0,
+                     static_cast<hipStream_t>(stream), in_y, in_u, in_v, h, in_stride_y, in_stride_c, fsel, fstep_y,
+                     fstep_c, g, out_y, out_u, out_v, strength, extra, extra_stride, out,
+                     static_cast<const SlotRoute*>(route));
+  return 1;
+}
+
 extern "C" void mivc_launch_qp_fixup(int B, int wmb, int hmb, void* hdr, const int16_t* coef, const uint8_t* nz,
-                                     uint8_t* flags, const int* slice_qp, void* stream, int slice_rows) {
+                                     uint8_t* flags, const int* slice_qp, void* stream, int slice_rows,
+                                     const uint8_t* pre, const void* route) {
   const Geom g{B, wmb, hmb, wmb * 16, hmb * 16};
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int rows = (slice_rows > 0 && slice_rows < hmb) ? slice_rows : hmb;
   const int per_slot = (hmb + rows - 1) / rows;
   hipLaunchKernelGGL(h264_qp_flags, dim3((wmb * hmb + 15) / 16, B), dim3(256), 0, s, g,
-                     static_cast<const mivc::h264::MbHeader*>(hdr), coef, nz, flags);
+                     static_cast<const mivc::h264::MbHeader*>(hdr), coef, nz, flags,
+                     (pre && route) ? pre : nullptr, static_cast<const SlotRoute*>(route));
   hipLaunchKernelGGL(h264_qp_fixup, dim3(B * per_slot), dim3(1024), 0, s, g, static_cast<mivc::h264::MbHeader*>(hdr),
                      flags, slice_qp, rows * wmb, per_slot);
 }

@@ -69,7 +69,11 @@ void mivc_launch_aq_offsets(int B, int wmb, int hmb, const uint8_t* sy, const ui
 void mivc_launch_mbtree(int B, int F, int lbw, int lbh, const int* blk_cost, const int* blk_mv, void* prop,
                         float strength, float* out, void* stream);
 void mivc_launch_qp_fixup(int B, int wmb, int hmb, void* hdr, const int16_t* coef, const uint8_t* nz, uint8_t* flags,
-                          const int* slice_qp, void* stream, int slice_rows);
+                          const int* slice_qp, void* stream, int slice_rows, const uint8_t* pre, const void* route);
+int mivc_launch_prep_aq(const uint8_t* in_y, const uint8_t* in_u, const uint8_t* in_v, int w, int h, int64_t in_stride_y,
+                        int64_t in_stride_c, int B, uint8_t* out_y, uint8_t* out_u, uint8_t* out_v, int W, int H,
+                        const int* fsel, float strength, const float* extra, long long extra_stride, int8_t* out,
+                        void* stream, const void* route);
 void mivc_launch_me_halfpel(int B, int W, int H, const uint8_t* ref_y, uint8_t* hp, void* stream, const void* route,
                             int nbuf);
 void mivc_launch_encode_inter(int B, int wmb, int hmb, const uint8_t* src_y, const uint8_t* src_u,
@@ -80,7 +84,8 @@ void mivc_launch_encode_inter(int B, int wmb, int hmb, const uint8_t* src_y, con
                               int* intra_count, const int8_t* aq, const uint8_t* ref1_u, const uint8_t* ref1_v,
                               int bmode, int t8, const int16_t* mv8, void* stream, const int* w1, int nref,
                               const uint8_t* const* xref_u, const uint8_t* const* xref_v, const int8_t* mref,
-                              const int* wp, int trellis, float trellis_lambda, const void* route, int nbuf);
+                              const int* wp, int trellis, float trellis_lambda, const void* route, int nbuf,
+                              uint8_t* qp_flags);
 void mivc_launch_wp_stats16(const uint16_t* y, const uint16_t* u, const uint16_t* v, int w, int h, int npics,
                             unsigned long long* out, void* stream);
 void mivc_launch_wp_stats(const uint8_t* y, const uint8_t* u, const uint8_t* v, int w, int h, int npics,
@@ -353,11 +358,27 @@ PYBIND11_MODULE(_hip, m) {
                        S(stream));
   });
   m.def("qp_fixup", [](int B, int wmb, int hmb, uintptr_t hdr, uintptr_t coef, uintptr_t nz, uintptr_t flags,
-                       uintptr_t slice_qp, uintptr_t stream, int slice_rows) {
+                       uintptr_t slice_qp, uintptr_t stream, int slice_rows, uintptr_t pre, uintptr_t route) {
+    // pre + route (both or none): encode_inter's per-MB bytes (its qp_flags argument) and the
+    // step's routing; slots coding a P / B picture take the 0 / 1 bytes as their flags
+    if ((pre != 0) != (route != 0)) throw std::invalid_argument("qp_fixup: pre and route go together");
     mivc_launch_qp_fixup(B, wmb, hmb, P<void>(hdr), P<int16_t>(coef), P<uint8_t>(nz), P<uint8_t>(flags),
-                         P<int>(slice_qp), S(stream), slice_rows);
+                         P<int>(slice_qp), S(stream), slice_rows, P<uint8_t>(pre), P<void>(route));
   }, py::arg("B"), py::arg("wmb"), py::arg("hmb"), py::arg("hdr"), py::arg("coef"), py::arg("nz"), py::arg("flags"),
-     py::arg("slice_qp"), py::arg("stream"), py::arg("slice_rows") = 0);
+     py::arg("slice_qp"), py::arg("stream"), py::arg("slice_rows") = 0, py::arg("pre") = 0, py::arg("route") = 0);
+  m.def("prep_aq", [](uintptr_t iy, uintptr_t iu, uintptr_t iv, int w, int h, int64_t sy, int64_t sc, int n,
+                      uintptr_t oy, uintptr_t ou, uintptr_t ov, int W, int H, float strength, uintptr_t out,
+                      uintptr_t stream, uintptr_t fsel, uintptr_t extra, long long extra_stride, uintptr_t route) {
+    // prep + aq_offsets in one launch; false (nothing launched) when the shapes or pointers are
+    // not those of its fast path: the caller then makes the two calls
+    if (W < w || H < h || w < 2 || h < 2) throw std::invalid_argument("prep_aq: bad geometry");
+    if (!out) throw std::invalid_argument("prep_aq: needs the offset buffer");
+    return mivc_launch_prep_aq(P<uint8_t>(iy), P<uint8_t>(iu), P<uint8_t>(iv), w, h, sy, sc, n, P<uint8_t>(oy),
+                               P<uint8_t>(ou), P<uint8_t>(ov), W, H, P<int>(fsel), strength, P<float>(extra),
+                               extra_stride, P<int8_t>(out), S(stream), P<void>(route)) != 0;
+  }, py::arg("iy"), py::arg("iu"), py::arg("iv"), py::arg("w"), py::arg("h"), py::arg("sy"), py::arg("sc"), py::arg("n"),
+     py::arg("oy"), py::arg("ou"), py::arg("ov"), py::arg("W"), py::arg("H"), py::arg("strength"), py::arg("out"),
+     py::arg("stream"), py::arg("fsel") = 0, py::arg("extra") = 0, py::arg("extra_stride") = 0, py::arg("route") = 0);
   m.def("me_halfpel", [](int B, int W, int H, uintptr_t ref, uintptr_t hp, uintptr_t stream, uintptr_t route, int nbuf) {
     if (route && nbuf < 1) throw std::invalid_argument("me_halfpel: a routed launch needs the pool size");
     mivc_launch_me_halfpel(B, W, H, P<uint8_t>(ref), P<uint8_t>(hp), S(stream), P<void>(route), nbuf);
@@ -370,7 +391,7 @@ PYBIND11_MODULE(_hip, m) {
            uintptr_t intra_flag, uintptr_t intra_count, uintptr_t stream, uintptr_t aq, uintptr_t ref1_u,
            uintptr_t ref1_v, int bmode, int t8, uintptr_t mv8, std::vector<int> w1, std::vector<uintptr_t> xref_u,
            std::vector<uintptr_t> xref_v, uintptr_t mref, uintptr_t wp, int trellis, float trellis_lambda,
-           uintptr_t route, int nbuf) {
+           uintptr_t route, int nbuf, uintptr_t qp_flags) {
           // xref_u / xref_v: chroma of RefPicList0[1..]; w1: implicit list-1 weight per list-0 picture
           if (bmode && (!ref1_u || !ref1_v)) throw std::invalid_argument("encode_inter: B mode needs the list-1 chroma");
           const size_t n = xref_u.size() + 1;
@@ -393,7 +414,7 @@ PYBIND11_MODULE(_hip, m) {
                                    P<int>(intra_count), P<int8_t>(aq), P<uint8_t>(ref1_u), P<uint8_t>(ref1_v), bmode,
                                    t8, P<int16_t>(mv8), S(stream), w.data(), static_cast<int>(n), xu, xv,
                                    bmode ? nullptr : P<int8_t>(mref), P<int>(wp), trellis, trellis_lambda, P<void>(route),
-                                   nbuf);
+                                   nbuf, P<uint8_t>(qp_flags));
         }, py::arg("B"), py::arg("wmb"), py::arg("hmb"), py::arg("sy"), py::arg("su"), py::arg("sv"), py::arg("fy"),
         py::arg("fu"), py::arg("fv"), py::arg("ry"), py::arg("ru"), py::arg("rv"), py::arg("pred"), py::arg("mv"),
         py::arg("me_cost"), py::arg("intra_cost"), py::arg("qp"), py::arg("cqo"), py::arg("hdr"), py::arg("coef"),
@@ -401,7 +422,7 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("ref1_u") = 0, py::arg("ref1_v") = 0, py::arg("bmode") = 0, py::arg("t8") = 0, py::arg("mv8") = 0,
         py::arg("w1") = std::vector<int>{32}, py::arg("xref_u") = std::vector<uintptr_t>{},
         py::arg("xref_v") = std::vector<uintptr_t>{}, py::arg("mref") = 0, py::arg("wp") = 0, py::arg("trellis") = 0,
-        py::arg("trellis_lambda") = 1.0f, py::arg("route") = 0, py::arg("nbuf") = 0);
+        py::arg("trellis_lambda") = 1.0f, py::arg("route") = 0, py::arg("nbuf") = 0, py::arg("qp_flags") = 0);
   m.def("wp_stats16", [](uintptr_t y, uintptr_t u, uintptr_t v, int w, int h, int npics, uintptr_t out, uintptr_t stream) {
     if (w % 2 || h % 2 || npics <= 0) throw std::invalid_argument("wp_stats16: even picture sizes, npics > 0");
     mivc_launch_wp_stats16(P<uint16_t>(y), P<uint16_t>(u), P<uint16_t>(v), w, h, npics, P<unsigned long long>(out),

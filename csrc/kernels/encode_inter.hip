@@ -60,6 +60,10 @@ struct InterArgs {
   // P (bmode 0) or B (bmode 1) picture take their roles and implicit weights from SlotRoute
   const SlotRoute* rt;
   int nbuf;
+  // [B, nmb] (nullable): per MB 1 = it has a luma, chroma AC or chroma DC level (it carries
+  // mb_qp_delta), 0 = none, 2 = handed to the intra kernels -- what h264_qp_flags would
+  // otherwise read back from the levels (aq.hip)
+  uint8_t* qp_flags;
 };
 
 // trellis_lite4x4 / trellis_lite8_chunk: h264_trellis.h
@@ -200,6 +204,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
   int lv[16];       // levels of this lane's block (raster; scan order of its chunk on the 8x8 path)
   int res[16];      // residual / reconstruction scratch
   uint32_t prw[4];  // prediction rows (4 bytes each)
+  uint64_t luma_any = 0;  // lanes whose luma block has a level (a 16-lane row per MB): for a.qp_flags
 
   // ================================================================ phase 1: luma
   {
@@ -477,6 +482,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
       if (any) h264::inverse_core4x4(res);
     }
     const bool t8_coded = ((__ballot(keep8) >> (16 * q)) & 0xFFFFu) != 0;  // the MB has 8x8 levels
+    luma_any = __ballot(any);  // (`any` is false outside `work`)
     if (work) {
       uint8_t* recy = a.rec_y + rcur * g.ysize() + static_cast<size_t>(Y0 + lby) * W + X0 + lbx;
 #pragma unroll
@@ -522,7 +528,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
     int mx, my, qpy;
     size_t o;
     bool work;
-    locate((lane >> 3) & 3, mx, my, o, work, qpy);
+    const bool live = locate((lane >> 3) & 3, mx, my, o, work, qpy);
     work = work && lane < 32;
     const MbHeader* h = a.hdr + o;
     int16_t* coef = a.coef + o * h264::kCoefPerMb;
@@ -602,6 +608,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
     const int d0 = quad_bcast<0>(dc), d1 = quad_bcast<1>(dc), d2 = quad_bcast<2>(dc), d3 = quad_bcast<3>(dc);
     const int score_c = sum4(score);
     const bool keep_ac = score_c >= 7;
+    bool any_c = false;  // this block has an AC level or its component a DC level
     if (work) {
       // chroma DC: 2x2 Hadamard + quantisation with qbits+1 (every lane of the quad: no hand-off)
       const int f[4] = {d0 + d1 + d2 + d3, d0 - d1 + d2 - d3, d0 + d1 - d2 - d3, d0 - d1 - d2 + d3};
@@ -629,6 +636,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
       for (int r = 0; r < 16; ++r) res[r] = (keep_ac && r > 0) ? (lv[r] * dvc[h264::kPosClass[r]]) << (qpc / 6) : 0;
       res[0] = ((fcb * ls) << (qpc / 6)) >> 5;
       const bool any = any_ac || c0 || c1 || c2 || c3;
+      any_c = any;
       if (any) h264::inverse_core4x4(res);
       uint8_t* recc = (comp == 0 ? a.rec_u : a.rec_v) + rcur * g.csize() + static_cast<size_t>(my * 8 + cby) * cw + mx * 8 + cbx;
 #pragma unroll
@@ -639,6 +647,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
           v4[x] = h264::clip1(static_cast<int>(__builtin_amdgcn_ubfe(prw[y], 8 * x, 8)) + (any ? res[y * 4 + x] : 0));
         *reinterpret_cast<uint32_t*>(recc + static_cast<size_t>(y) * cw) = pack4_u8(v4);
       }
+    }
+    if (a.qp_flags) {
+      // MB m of the wave: luma on lanes 16 m .. 16 m + 15 of phase 1, chroma on lanes 8 m .. 8 m + 7
+      const uint64_t chroma_any = __ballot(any_c);
+      const int m = (lane >> 3) & 3;
+      if (live && lane < 32 && (lane & 7) == 0)
+        a.qp_flags[o] = !work ? 2 : ((((luma_any >> (16 * m)) & 0xFFFFu) | ((chroma_any >> (8 * m)) & 0xFFu)) != 0 ? 1 : 0);
     }
   }
 }
@@ -658,8 +673,9 @@ extern "C" void mivc_launch_encode_inter(int B, int wmb, int hmb, const uint8_t*
                                          int t8, const int16_t* mv8, void* stream, const int* w1, int nref,
                                          const uint8_t* const* xref_u, const uint8_t* const* xref_v,
                                          const int8_t* mref, const int* wp, int trellis, float trellis_lambda,
-                                         const void* route, int nbuf) {
+                                         const void* route, int nbuf, uint8_t* qp_flags) {
   InterArgs a;
+  a.qp_flags = qp_flags;
   a.rt = static_cast<const SlotRoute*>(route);
   a.nbuf = nbuf;
   a.trellis = trellis;

@@ -498,6 +498,7 @@ class GpuH264Encoder:
         self.intra_flag = torch.zeros((B, nmb), dtype=u8, device=dev)
         self.aq = torch.zeros((B, nmb), dtype=torch.int8, device=dev)     # per-MB QP offsets (AQ)
         self.qp_flags = torch.zeros((B, nmb), dtype=u8, device=dev)       # MB carries mb_qp_delta
+        self.qp_pre = torch.zeros((B, nmb), dtype=u8, device=dev)         # ... as encode_inter saw it (0 / 1; 2: intra)
         self.intra_count = torch.zeros((B,), dtype=i32, device=dev)
         self.qp = torch.zeros((B,), dtype=i32, device=dev)
         # error flags, one buffer per batch in flight (encode_async: the next batch zeroes its own
@@ -627,16 +628,40 @@ class GpuH264Encoder:
                       self._ptr(self.src[0]), self._ptr(self.src[1]), self._ptr(self.src[2]),
                       self.p.width, self.p.height, self.W, self.H, self._stream())
 
-    def _prep_step(self, y, u, v, disp: np.ndarray, disp_d: torch.Tensor):
+    def _mbtree_rows(self) -> tuple[int, int]:
+        """(pointer, slot stride) of the batch's MB-tree offsets for the AQ kernels, (0, 0) without.
+        They belong to referenced pictures: the routing picks each slot's row."""
+        mbt = self._mbtree
+        if mbt is not None and mbt.shape[2] == self.nmb:
+            return mbt.data_ptr(), mbt.shape[1] * self.nmb
+        return 0, 0
+
+    def _prep_step(self, y, u, v, disp: np.ndarray, disp_d: torch.Tensor, st: dict | None = None):
         """Pad each slot's display picture of this coding step (``disp``: [B] display indices,
-        ``disp_d`` the same on the device): one launch, per-slot frame selection."""
-        if (disp == disp[0]).all():
-            return self._prep(y, u, v, int(disp[0]))
+        ``disp_d`` the same on the device): one launch, per-slot frame selection.  With the
+        step's tables ``st`` and variance AQ on, the same launch writes the AQ offsets
+        (``st["aq_done"]``) where the kernel library has it and takes the shapes."""
         B, F, h, w = y.shape
         cs = u.shape[2] * u.shape[3]
-        self.hip.prep(y.data_ptr(), u.data_ptr(), v.data_ptr(), w, h, F * h * w, F * cs, B,
-                      self._ptr(self.src[0]), self._ptr(self.src[1]), self._ptr(self.src[2]),
-                      self.p.width, self.p.height, self.W, self.H, self._stream(), disp_d.data_ptr())
+        same = bool((disp == disp[0]).all())
+        with self.stage_timer("prep"):
+            if st is not None:
+                st["aq_done"] = False
+                if self.p.aq_strength > 0 and hasattr(self.hip, "prep_aq"):
+                    t = int(disp[0]) if same else 0
+                    extra, stride = self._mbtree_rows()
+                    st["aq_done"] = self.hip.prep_aq(
+                        y[:, t].data_ptr(), u[:, t].data_ptr(), v[:, t].data_ptr(), w, h, F * h * w, F * cs, B,
+                        self._ptr(self.src[0]), self._ptr(self.src[1]), self._ptr(self.src[2]), self.W, self.H,
+                        float(self.p.aq_strength), self._ptr(self.aq), self._stream(),
+                        0 if same else disp_d.data_ptr(), extra, stride, st["route"])
+                    if st["aq_done"]:
+                        return
+            if same:
+                return self._prep(y, u, v, int(disp[0]))
+            self.hip.prep(y.data_ptr(), u.data_ptr(), v.data_ptr(), w, h, F * h * w, F * cs, B,
+                          self._ptr(self.src[0]), self._ptr(self.src[1]), self._ptr(self.src[2]),
+                          self.p.width, self.p.height, self.W, self.H, self._stream(), disp_d.data_ptr())
 
     @staticmethod
     def _dist_scale(poc: int, poc0: int, poc1: int) -> tuple[int, int]:
@@ -671,14 +696,15 @@ class GpuH264Encoder:
         stt = self.stage_timer
         if self.p.aq_strength > 0 or mbt is not None:
             aq = P(self.aq)
-            extra, stride = 0, 0
-            # MB-tree offsets belong to referenced pictures (the routing picks each slot's row)
-            if mbt is not None and mbt.shape[2] == self.nmb:
-                extra, stride = mbt.data_ptr(), mbt.shape[1] * self.nmb
-            with stt("aq"):
-                self.hip.aq_offsets(B, wmb, hmb, sy, su, sv, float(self.p.aq_strength), aq, s, extra, stride, rt)
+            if not st.get("aq_done"):  # (else: written with the padding, _prep_step)
+                extra, stride = self._mbtree_rows()
+                with stt("aq"):
+                    self.hip.aq_offsets(B, wmb, hmb, sy, su, sv, float(self.p.aq_strength), aq, s, extra, stride, rt)
         cqo = self.p.chroma_qp_offset
         inter = st["P"] or st["B"]
+        # encode_inter leaves the mb_qp_delta flag of its MBs for qp_fixup (a kernel library from
+        # before that argument computes them all from the levels, as on I-picture steps)
+        pre = {"qp_flags": P(self.qp_pre)} if (aq and inter and hasattr(self.hip, "prep_aq")) else {}
         if inter:
             self.intra_count.zero_()
         seed0 = seed1 = 0
@@ -749,7 +775,7 @@ class GpuH264Encoder:
                                       P(self.nz), P(self.intra_flag), P(self.intra_count), s, aq,
                                       t8=int(self.p.eff_t8x8()), mv8=mv8, mref=P(self.mref), wp=wp,
                                       trellis=int(self.p.trellis), trellis_lambda=float(self.p.trellis_lambda),
-                                      route=rt, nbuf=NB)
+                                      route=rt, nbuf=NB, **pre)
         if st["B"]:
             br = self.p.b_me_range
             spatial = self.p.direct == "spatial"
@@ -799,7 +825,7 @@ class GpuH264Encoder:
                                       P(self.cost_b), P(self.intra_cost), P(self.qp), cqo, P(hdr), P(coef),
                                       P(self.nz), P(self.intra_flag), P(self.intra_count), s, aq, pu, pv, 1,
                                       int(self.p.eff_t8x8()), 0, [32], [], [], 0, 0, int(self.p.trellis),
-                                      float(self.p.trellis_lambda), rt, NB)
+                                      float(self.p.trellis_lambda), rt, NB, **pre)
         if inter:
             self.p_intra_mbs += self.intra_count.sum()
             flag_ptr, count_ptr = P(self.intra_flag), P(self.intra_count)
@@ -821,7 +847,13 @@ class GpuH264Encoder:
         if aq:
             # MBs without mb_qp_delta take QP_pred (clause 7.4.5): their records must say so
             # before deblocking reads every MB's QP
-            self.hip.qp_fixup(B, wmb, hmb, P(hdr), P(coef), P(self.nz), P(self.qp_flags), P(self.qp), s, self.slice_rows)
+            with stt("qp_fixup"):
+                if pre:
+                    self.hip.qp_fixup(B, wmb, hmb, P(hdr), P(coef), P(self.nz), P(self.qp_flags), P(self.qp), s,
+                                      self.slice_rows, pre=pre["qp_flags"], route=rt)
+                else:
+                    self.hip.qp_fixup(B, wmb, hmb, P(hdr), P(coef), P(self.nz), P(self.qp_flags), P(self.qp), s,
+                                      self.slice_rows)
         # A non-reference B picture's reconstruction feeds nothing but its own intra MBs
         # (which predict from unfiltered samples), so its in-loop filter only matters when
         # someone looks at the picture: metrics (PSNR / SSIM) or keep_recon.  The bitstream
@@ -1576,7 +1608,7 @@ class GpuH264Encoder:
             self.timings["host_blocked_s"] = self.timings.get("host_blocked_s", 0.0) + time.perf_counter() - tw
             # (steps 0 / 1: the previous batch's last steps, when it is still in flight)
             main.wait_event(self.copy_done[k])
-            self._prep_step(y, u, v, orders[:, t], orders_d[t])
+            self._prep_step(y, u, v, orders[:, t], orders_d[t], st)
             st["disp_d"] = orders_d[t]
             self.qp.copy_(qps_d[t])
             self._encode_step(st, self.hdr[k], self.coef[k], cuts_d[t] if (t > 0 and cuts_c[:, t].any()) else None)

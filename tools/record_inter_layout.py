@@ -2,7 +2,8 @@
 """Record the golden bitstream hashes of tests/test_gpu_inter_layout.py (suite ``inter``),
 tests/test_gpu_decide_layout.py (suite ``decide``), tests/test_gpu_gate_layout.py (suite ``gate``)
 and tests/test_gpu_intra_free.py (suite ``intra``: planted intra MBs of P / B pictures, with the
-counts of free and chained ones per case).
+counts of free and chained ones per case) and tests/test_gpu_source_pass.py (suite ``source``: the
+clips of the padding / AQ and mb_qp_delta flag tests through ``encode``).
 
 The tests pin the bytes of small encodes, at shapes where the four-MBs-per-wave lane layout can
 go wrong, to what the *parent* build of the kernels emits.  So this recorder never runs on the
@@ -14,6 +15,7 @@ commit, e.g.
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py decide tests/golden/decide_layout_parent.json
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py gate tests/golden/gate_layout_parent.json
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py intra tests/golden/intra_free_parent.json
+    MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py source tests/golden/source_pass_parent.json
 
 The file holds, per case, the arguments (size, frames, clip seed / class, parameter overrides)
 and the SHA-256 of every slot's bitstream.  Per case it also prints what the test asserts
@@ -179,6 +181,29 @@ INTRA_CASES = [
          params=dict(crf=None, qp=18, t8x8=True, trellis=2, aq_strength=1.0, **_P)),
     dict(id="176x144-b-noise-lowqp", width=176, height=144, frames=9, seed=11, clip="synth", kind="noise", pics=None,
          need=["free", "chained"], params=dict(crf=None, qp=16, t8x8=True, trellis=2, aq_strength=1.0, **_B3)),
+]
+
+# The source pass (aq.hip prep_aq_rows) and the mb_qp_delta flags of encode_inter: see
+# tests/test_gpu_source_pass.py, whose clip builders this suite runs.  planes-*: random bytes at
+# the shapes of the padding test (one with per-slot plans: every slot pads another display
+# picture); flags-*: static noise with one changed and one intra-predictable MB per frame, 9 and
+# 15 MBs (one and three live MBs in the last wave), one with per-slot plans: a slot codes a P
+# picture while the other codes a B picture.
+_SRC = dict(crf=None, qp=32, aq_strength=1.0, bframes=0)
+_FLG = dict(crf=None, qp=26, aq_strength=1.0, bframes=3, lookahead=False)
+SOURCE_CASES = [
+    dict(id=f"planes-{w}x{h}", clip="random", width=w, height=h, slots=3, frames=4, seed=31 + i, params=dict(_SRC))
+    for i, (w, h) in enumerate([(48, 32), (48, 24), (48, 18), (16, 24), (1040, 24), (40, 24)])
+] + [
+    dict(id="planes-48x24-per-slot-plans", clip="random", width=48, height=24, slots=3, frames=4, seed=41,
+         anchors_at=[[2], [], [3]], params=dict(_SRC, bframes=2, lookahead=False)),
+] + [
+    dict(id=f"flags-{w}x48-trellis{tr}", clip="flags", width=w, height=48, slots=2, frames=6, seed=51 + i,
+         need_flags=True, params=dict(_FLG, trellis=tr))
+    for i, (w, tr) in enumerate([(48, 0), (48, 2), (80, 0), (80, 2)])
+] + [
+    dict(id="flags-80x48-per-slot-plans", clip="flags", width=80, height=48, slots=2, frames=6, seed=61,
+         anchors_at=[[3], [2]], need_flags=True, params=dict(_FLG, trellis=2)),
 ]
 
 INTRA_KINDS = (0, 1, 4, 8)
@@ -351,6 +376,30 @@ def record_intra(host, path) -> None:
         f.write("\n")
 
 
+def record_source(host, path) -> None:
+    """Suite ``source``: per case the per-slot hashes.  The clips are the test's own (the test
+    module reads the golden file when imported, so a first recording starts from an empty one)."""
+    import numpy as np
+
+    if not os.path.exists(path):
+        with open(path, "w") as f:
+            json.dump(dict(cases=[]), f)
+    from tests import test_gpu_source_pass as T
+
+    rows = []
+    for case in SOURCE_CASES:
+        case = json.loads(json.dumps(case))  # as the test will read it
+        enc, res, _ = T._encode(case)
+        streams = [bytes(r.bitstream) for r in res]
+        kinds = [np.unique(np.asarray(seg["hdr"])[:, :, 0]).tolist() for seg in host.parse(streams, 1)]
+        enc.close()
+        print(case["id"], [len(s) for s in streams], "MB kinds per slot", kinds, flush=True)
+        rows.append(dict(case, sha256=[hashlib.sha256(s).hexdigest() for s in streams]))
+    with open(path, "w") as f:
+        json.dump(dict(cases=rows), f, indent=1)
+        f.write("\n")
+
+
 def np_isin_any(a, values) -> bool:
     import numpy as np
 
@@ -359,7 +408,7 @@ def np_isin_any(a, values) -> bool:
 
 def main() -> None:
     suite = "inter"
-    if len(sys.argv) == 3 and sys.argv[1] in ("inter", "decide", "gate", "intra"):
+    if len(sys.argv) == 3 and sys.argv[1] in ("inter", "decide", "gate", "intra", "source"):
         suite = sys.argv.pop(1)
     if len(sys.argv) != 2:
         raise SystemExit(__doc__)
@@ -372,6 +421,9 @@ def main() -> None:
     rows = []
     if suite == "intra":
         record_intra(host, sys.argv[1])
+        return
+    if suite == "source":
+        record_source(host, sys.argv[1])
         return
     if suite == "gate":
         for case in GATE_CASES:
