@@ -11,6 +11,7 @@
 
 #include "../common/hevc_ctu_coder.h"
 #include "hevc_decode.h"
+#include "route.h"
 
 namespace py = pybind11;
 
@@ -44,7 +45,7 @@ void mivc_launch_b_spatial(int B, int wmb, int hmb, void* hdr, const void* col, 
                            const int* qp, const int8_t* aq, int bias, const void* route, int nbuf);
 void mivc_launch_b_direct(int B, int wmb, int hmb, const void* col, const int* dsf, const int* direct_copy, int nref,
                           int16_t* dmv, int8_t* dref, int16_t* pm0, int16_t* pm1, void* stream, const void* route,
-                          int nbuf, uint8_t* czero);
+                          int nbuf, uint8_t* czero, const int8_t* cmap);
 void mivc_launch_b_spatial_exact(int B, int wmb, int hmb, void* hdr, const int* intra_cost, const int* cost,
                                  const uint8_t* czero, uint8_t* fix, void* stream, const void* route, int slice_rows,
                                  int tol);
@@ -196,6 +197,8 @@ void* S(uintptr_t s) { return reinterpret_cast<void*>(s); }
 PYBIND11_MODULE(_hip, m) {
   m.doc() = "govideocompressor_amd gfx950 kernels (raw-pointer launch shims)";
   m.attr("arch") = "gfx950";
+  // sizeof(SlotRoute): the row size the routed kernels step by (ROUTE_DTYPE in models/h264_gpu.py)
+  m.def("route_bytes", []() { return static_cast<int>(sizeof(mivc::gpu::SlotRoute)); });
 
   m.def("synth", [](uintptr_t y, uintptr_t u, uintptr_t v, int w, int h, int slots, int frames, int frame0,
                     uint32_t seed, uintptr_t stream, int bit_depth, int slot0, int kind) {
@@ -273,16 +276,19 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("route") = 0, py::arg("nbuf") = 0);
   m.def("b_direct", [](int B, int wmb, int hmb, uintptr_t col, std::vector<int> dsf, std::vector<int> direct_copy,
                        uintptr_t dmv, uintptr_t pm0, uintptr_t pm1, uintptr_t stream, uintptr_t dref, uintptr_t route,
-                       int nbuf, uintptr_t czero) {
+                       int nbuf, uintptr_t czero, uintptr_t cmap) {
+    // cmap: [B, 2, 4] int8 MapColToList0 offsets of the step (route.h; 0: identity).  A mapped
+    // index needs dref to carry it (and -1 for quadrants without a direct prediction)
     if (dsf.empty() || dsf.size() > 4 || dsf.size() != direct_copy.size())
       throw std::invalid_argument("b_direct: one (dsf, direct_copy) pair per list-0 picture, at most 4");
     if (route && nbuf < 1) throw std::invalid_argument("b_direct: a routed launch needs the pool size");
+    if (cmap && !dref) throw std::invalid_argument("b_direct: a co-located map needs the dref output");
     mivc_launch_b_direct(B, wmb, hmb, P<void>(col), dsf.data(), direct_copy.data(), static_cast<int>(dsf.size()),
                          P<int16_t>(dmv), P<int8_t>(dref), P<int16_t>(pm0), P<int16_t>(pm1), S(stream), P<void>(route),
-                         nbuf, P<uint8_t>(czero));
+                         nbuf, P<uint8_t>(czero), P<int8_t>(cmap));
   }, py::arg("B"), py::arg("wmb"), py::arg("hmb"), py::arg("col"), py::arg("dsf"), py::arg("direct_copy"),
      py::arg("dmv"), py::arg("pm0"), py::arg("pm1"), py::arg("stream"), py::arg("dref") = 0, py::arg("route") = 0,
-     py::arg("nbuf") = 0, py::arg("czero") = 0);
+     py::arg("nbuf") = 0, py::arg("czero") = 0, py::arg("cmap") = 0);
   m.def("b_spatial_exact", [](int B, int wmb, int hmb, uintptr_t hdr, uintptr_t intra_cost, uintptr_t cost,
                               uintptr_t czero, uintptr_t fix, uintptr_t stream, uintptr_t route, int slice_rows,
                               int tol) {

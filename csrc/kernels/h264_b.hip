@@ -6,6 +6,13 @@
 // depends only on the co-located macroblock of RefPicList1[0] and on POC distances (clause
 // 8.4.1.2.3), never on its neighbours in the current picture, so every MB of every slot decides
 // in parallel (spatial direct needs the neighbours' final motion: a raster-order dependency).
+// That holds with a b-pyramid too: the co-located picture may then be the run's reference B
+// (list-0 indices of its own, list-1-only blocks pointing at the next anchor), or a reference B
+// stands in front of the anchors in list 0, so refIdxCol goes through each slot's
+// MapColToList0 table (route.h col_to_list0).  A quadrant whose co-located reference is not in
+// the current list 0 has no direct prediction (dref -1): its MB is never gated or coded
+// B_Direct_16x16 / B_Skip, and only its other quadrants may be B_Direct_8x8 -- a stream that
+// never asks the decoder for such a quadrant's direct motion is conforming.
 //
 //   b_direct_mv  (thread per MB)     direct MVs per list / 8x8 quadrant + the ME predictors
 //   b_decide     (four MBs per wave) candidates B_L0_16x16 / B_L1_16x16 (the two ME searches),
@@ -32,15 +39,22 @@ constexpr int kMaxRefs = 4;  // list-0 pictures an encoder P picture may referen
 
 struct BDirectArgs {
   Geom g;
-  const MbHeader* col;      // [B, nmb] records of RefPicList1[0] (a P anchor)
-  // per refIdxL0 r = refIdxCol (the anchor's list 0 and the B picture's list 0 order the same
-  // past anchors, so MapColToList0 is the identity): DistScaleFactor, ignored when direct_copy
+  const MbHeader* col;      // [B, nmb] records of RefPicList1[0] (a P anchor, or a reference B)
+  // per refIdxL0 = MapColToList0(refIdxCol): DistScaleFactor, ignored when direct_copy.  Without
+  // cmap the map is the identity (the anchor's list 0 and the B picture's list 0 order the same
+  // past anchors); with a b-pyramid (a reference B in front of the anchors in list 0, or as the
+  // co-located picture with lists of its own) it is each slot's table (route.h col_to_list0)
   int dsf[kMaxRefs];
   int direct_copy[kMaxRefs];  // td == 0: mvL0 = mvCol, mvL1 = 0
   int16_t* dmv;             // [B, nmb, 2, 4, 2] direct vectors (list, quadrant, xy)
-  int8_t* dref;             // [B, nmb, 4] refIdxL0 of each quadrant's direct prediction (nullable: all 0)
-  int16_t* pm0;             // [B, nmb, 2] ME predictor L0 (mean of the direct vectors)
-  int16_t* pm1;             // [B, nmb, 2] ME predictor L1
+  // [B, nmb, 4] refIdxL0 of each quadrant's direct prediction (nullable: all 0); -1 = the
+  // quadrant has no temporal direct prediction (its co-located reference is not in list 0:
+  // zero vectors, and b_decide never codes it direct)
+  int8_t* dref;
+  // [B, nmb, 2] ME predictors L0 / L1: the mean (rounded half up) of the direct vectors of the
+  // quadrants that have a direct prediction, zero when none has
+  int16_t* pm0;
+  int16_t* pm1;
   // routed (route.h): col is the record pool [B, nbuf, nmb]; B slots only, each with its own
   // co-located picture (RefPicList1[0]) and its own dsf / direct_copy (SlotRoute)
   const SlotRoute* rt;
@@ -48,7 +62,24 @@ struct BDirectArgs {
   // spatial direct (nullable): colZeroFlag of the four quadrants (bit q; 8.4.1.2.2: the
   // co-located block is inter, its refIdxCol is 0 and both vector components are in -1..1)
   uint8_t* czero;
+  const int8_t* cmap;  // [B, 2, 4] MapColToList0 offsets (route.h; nullable: identity)
 };
+
+// floor(s / n + 1/2) for n = 0..4 summands (0 for none): the ME predictor over the quadrants
+// that have a direct prediction; n = 4 is (s + 2) >> 2
+__device__ __forceinline__ int mean_half_up(int s, int n) {
+  if (n == 4) return (s + 2) >> 2;
+  if (n == 3) {
+    const int x = 2 * s + 3, d = x / 6;
+    return d - (x - d * 6 < 0 ? 1 : 0);
+  }
+  return n == 2 ? (s + 1) >> 1 : (n == 1 ? s : 0);
+}
+
+// The four quadrants' "no temporal direct prediction" bits of a dref word (bytes of -1)
+__device__ __forceinline__ uint32_t dref_unavail(uint32_t drw) {
+  return ((drw >> 7) & 1u) | ((drw >> 14) & 2u) | ((drw >> 21) & 4u) | ((drw >> 28) & 8u);
+}
 
 __global__ __launch_bounds__(256) void b_direct_mv(BDirectArgs a) {
   const int mb = blockIdx.x * 256 + threadIdx.x, slot = blockIdx.y;
@@ -63,7 +94,7 @@ __global__ __launch_bounds__(256) void b_direct_mv(BDirectArgs a) {
   int v[2][4][2];
   int rq[4];
   int s[2][2] = {{0, 0}, {0, 0}};
-  int cz = 0;
+  int cz = 0, navail = 0;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     // direct_8x8_inference: the corner 4x4 block of co-located quadrant q, i.e. its vector;
@@ -72,9 +103,15 @@ __global__ __launch_bounds__(256) void b_direct_mv(BDirectArgs a) {
     const bool none = intra || c.ref[cl][q] < 0;
     const int cx = none ? 0 : c.mv[cl][q][0];
     const int cy = none ? 0 : c.mv[cl][q][1];
-    const int r = none ? 0 : min(static_cast<int>(c.ref[cl][q]), kMaxRefs - 1);
-    rq[q] = r;
-    if (!none && c.ref[cl][q] == 0 && abs(cx) <= 1 && abs(cy) <= 1) cz |= 1 << q;
+    // refIdxCol, then MapColToList0: the index in this picture's list 0 of the picture the
+    // co-located block referred to (an intra co-located block: refIdxL0 0, zero vectors)
+    const int rc = none ? 0 : min(static_cast<int>(c.ref[cl][q]), kMaxRefs - 1);
+    const int rm = none ? 0 : col_to_list0(a.cmap, slot, cl, rc);
+    const bool una = rm < 0;  // not in list 0: no direct prediction for this quadrant
+    const int r = una ? 0 : rm;
+    rq[q] = rm;
+    navail += una ? 0 : 1;
+    if (!none && c.ref[cl][q] == 0 && abs(cx) <= 1 && abs(cy) <= 1) cz |= 1 << q;  // (on refIdxCol)
     int l0x, l0y;
     const int dcp = a.rt ? a.rt[slot].dcopy[r] : a.direct_copy[r], dsf = a.rt ? a.rt[slot].dsf[r] : a.dsf[r];
     if (dcp) {
@@ -84,10 +121,10 @@ __global__ __launch_bounds__(256) void b_direct_mv(BDirectArgs a) {
       l0x = (dsf * cx + 128) >> 8;
       l0y = (dsf * cy + 128) >> 8;
     }
-    v[0][q][0] = l0x;
-    v[0][q][1] = l0y;
-    v[1][q][0] = dcp ? 0 : l0x - cx;
-    v[1][q][1] = dcp ? 0 : l0y - cy;
+    v[0][q][0] = una ? 0 : l0x;
+    v[0][q][1] = una ? 0 : l0y;
+    v[1][q][0] = (una || dcp) ? 0 : l0x - cx;
+    v[1][q][1] = (una || dcp) ? 0 : l0y - cy;
 #pragma unroll
     for (int l = 0; l < 2; ++l) {
       s[l][0] += v[l][q][0];
@@ -103,15 +140,15 @@ __global__ __launch_bounds__(256) void b_direct_mv(BDirectArgs a) {
       d[l * 8 + q * 2 + 1] = static_cast<int16_t>(v[l][q][1]);
     }
   if (a.dref) {
-    const uint32_t rw = static_cast<uint32_t>(rq[0]) | (static_cast<uint32_t>(rq[1]) << 8) |
-                        (static_cast<uint32_t>(rq[2]) << 16) | (static_cast<uint32_t>(rq[3]) << 24);
+    const uint32_t rw = (static_cast<uint32_t>(rq[0]) & 255u) | ((static_cast<uint32_t>(rq[1]) & 255u) << 8) |
+                        ((static_cast<uint32_t>(rq[2]) & 255u) << 16) | (static_cast<uint32_t>(rq[3]) << 24);
     *reinterpret_cast<uint32_t*>(a.dref + o * 4) = rw;
   }
   if (a.czero) a.czero[o] = static_cast<uint8_t>(cz);
-  a.pm0[o * 2] = static_cast<int16_t>((s[0][0] + 2) >> 2);
-  a.pm0[o * 2 + 1] = static_cast<int16_t>((s[0][1] + 2) >> 2);
-  a.pm1[o * 2] = static_cast<int16_t>((s[1][0] + 2) >> 2);
-  a.pm1[o * 2 + 1] = static_cast<int16_t>((s[1][1] + 2) >> 2);
+  a.pm0[o * 2] = static_cast<int16_t>(mean_half_up(s[0][0], navail));
+  a.pm0[o * 2 + 1] = static_cast<int16_t>(mean_half_up(s[0][1], navail));
+  a.pm1[o * 2] = static_cast<int16_t>(mean_half_up(s[1][0], navail));
+  a.pm1[o * 2 + 1] = static_cast<int16_t>(mean_half_up(s[1][1], navail));
 }
 
 struct BDecideArgs {
@@ -164,13 +201,14 @@ struct BDecideArgs {
 // Bits: sub_mb_type (direct 1, L0 / L1 3, bi 5 bins), one full mvd per list in use, 1 bin
 // per later partition repeating it, and the B_8x8 mb_type (~6 bins) / 16x8 pair codes.
 // qsat: [candidate 0 direct, 1 bi, 2 L0, 3 L1][quadrant]; best / qm / kind: the 16x16 choice,
-// replaced when the split wins
-__device__ __forceinline__ void b_part_choice(const int (&qsat)[4][4], int lambda, bool no_direct, int mvb0, int mvb1,
+// replaced when the split wins.  no_direct: bit q = quadrant q may not be B_Direct_8x8 (all
+// four: spatial direct decided later; some: no temporal direct prediction there, dref -1)
+__device__ __forceinline__ void b_part_choice(const int (&qsat)[4][4], int lambda, uint32_t no_direct, int mvb0, int mvb1,
                                               int& best, int (&qm)[4], int& kind) {
   int sum = 0, used0 = 0, used1 = 0, pm[4];
 #pragma unroll
   for (int qq = 0; qq < 4; ++qq) {
-    const int cd = no_direct ? kNoCost : qsat[0][qq] + lambda * 1, cb = qsat[1][qq] + lambda * 7;
+    const int cd = ((no_direct >> qq) & 1u) ? kNoCost : qsat[0][qq] + lambda * 1, cb = qsat[1][qq] + lambda * 7;
     const int c0q = qsat[2][qq] + lambda * 4, c1q = qsat[3][qq] + lambda * 4;
     int m = 0, bc = cd;
     if (cb < bc) { m = 1; bc = cb; }
@@ -255,7 +293,9 @@ __device__ __forceinline__ void b_decide_main(const BDecideArgs& a, const MbRow&
   const int mvb0 = mvbits_se(m0x - a.pm0[o * 2]) + mvbits_se(m0y - a.pm0[o * 2 + 1]);
   const int mvb1 = mvbits_se(m1x - a.pm1[o * 2]) + mvbits_se(m1y - a.pm1[o * 2 + 1]);
   const int c_bi = satd_bi + lambda * (6 + mvb0 + mvb1);
-  const bool no_direct = a.spatial == 1;  // (searched)
+  // quadrants that may not be direct: all with spatial == 1 (searched), else those without a
+  // temporal direct prediction -- B_Direct_16x16 / B_Skip needs all four
+  const uint32_t no_direct = a.spatial == 1 ? 15u : (a.spatial == 2 ? 0u : dref_unavail(drw));
   const int dbias = no_direct ? 0 : a.dbias * lambda;
   int mode = 0, best = no_direct ? kNoCost : c_direct - dbias;  // 0 direct, 1 L0, 2 L1, 3 Bi
   if (c_l0 < best) { mode = 1; best = c_l0; }
@@ -355,8 +395,12 @@ __global__ __launch_bounds__(64) void b_decide(BDecideArgs a) {
   const bool have_direct = K == 2 ? true : ((K == 1 || K == 3) ? false : static_cast<bool>(a.have_direct));
   const bool sfast = a.spatial == 2;
   MbHeader* hrec = a.hdr + o;
-  uint32_t drw = 0;  // refIdxL0 of the four temporal-direct quadrants (bytes)
+  uint32_t drw = 0;  // refIdxL0 of the four temporal-direct quadrants (bytes; -1: no direct prediction)
   if (a.dref) drw = *reinterpret_cast<const uint32_t*>(a.dref + o * 4);
+  // quadrants without a temporal direct prediction (b-pyramid: the co-located reference is not
+  // in list 0).  Such an MB is never gated (the pre-passes leave kNoCost, so both searches run)
+  // and is direct only in its other quadrants (B_Direct_8x8)
+  const uint32_t una = sfast ? 0u : dref_unavail(drw);
   // gated MB (the search left kNoCost): B_Direct_16x16 with the pre-pass's prediction and cost
   auto direct_record = [&]() {
     if (lane == 0) {
@@ -396,7 +440,7 @@ __global__ __launch_bounds__(64) void b_decide(BDecideArgs a) {
   } else if (!sfast) {
 #pragma unroll
     for (int qq = 0; qq < 4; ++qq) {
-      dref_[0][qq] = (drw >> (8 * qq)) & 255;
+      dref_[0][qq] = static_cast<int8_t>((drw >> (8 * qq)) & 255u);  // (-1: priced from list 1 alone, never chosen)
       dref_[1][qq] = 0;
       dvx[0][qq] = dm[qq * 2];
       dvy[0][qq] = dm[qq * 2 + 1];
@@ -466,7 +510,8 @@ __global__ __launch_bounds__(64) void b_decide(BDecideArgs a) {
   }
   if constexpr (K == 3) {
     // the temporal-direct pre-pass: this lane's quadrant only
-    const int dr = (drw >> (8 * q)) & 255;
+    // (a quadrant without a direct prediction: entry 0 with its zero vectors, never chosen)
+    const int dr = max(static_cast<int>(static_cast<int8_t>((drw >> (8 * q)) & 255u)), 0) & 3;
     const int dvx0 = dm[q * 2], dvy0 = dm[q * 2 + 1], dvx1 = dm[8 + q * 2], dvy1 = dm[8 + q * 2 + 1];
     const size_t sd = route_index(a.rt, a.nbuf, slot, RO_L0 + (dr & 3));
     const uint8_t *GD = dr ? a.ref0k[dr] + (a.rt ? sd : slot) * g.ysize() : G0,
@@ -479,7 +524,7 @@ __global__ __launch_bounds__(64) void b_decide(BDecideArgs a) {
       *reinterpret_cast<uint32_t*>(pout + 16 * y) = pd[y];
     }
     const int sat = row_satd(src, pd);
-    if (lane == 0) a.cost_out[o] = sat + mb_lambda(a.qp, a.aq, slot, o) * 1;
+    if (lane == 0) a.cost_out[o] = (drw & 0x80808080u) ? kNoCost : sat + mb_lambda(a.qp, a.aq, slot, o) * 1;
     return;
   }
   const int dr = dref_[0][q] < 0 ? 0 : dref_[0][q];  // this lane's quadrant
@@ -539,12 +584,12 @@ __global__ __launch_bounds__(64) void b_decide(BDecideArgs a) {
         // spatial direct decided in the wavefront (b_spatial_decide): only MBs whose co-located
         // motion is static in every quadrant (temporal direct vectors within +-1, refIdxL0 0)
         // may skip the searches -- there spatial direct predicts zero motion too (colZeroFlag)
-        bool stat = drw == 0;
+        bool stat = drw == 0;  // (so every quadrant has its direct prediction)
 #pragma unroll
         for (int k = 0; k < 16; ++k) stat = stat && dm[k] >= -1 && dm[k] <= 1;
         a.cost_out[o] = stat ? c_direct : kNoCost;
       } else {
-        a.cost_out[o] = c_direct;
+        a.cost_out[o] = una ? kNoCost : c_direct;
       }
       if (sfast) {  // the estimate, for the main pass (and for gated MBs: their motion)
 #pragma unroll
@@ -564,7 +609,7 @@ __global__ __launch_bounds__(64) void b_decide(BDecideArgs a) {
   const int mvb0 = mvbits_se(m0x - a.pm0[o * 2]) + mvbits_se(m0y - a.pm0[o * 2 + 1]);
   const int mvb1 = mvbits_se(m1x - a.pm1[o * 2]) + mvbits_se(m1y - a.pm1[o * 2 + 1]);
   const int c_bi = satd_bi + lambda * (6 + mvb0 + mvb1);
-  const bool no_direct = a.spatial == 1 && searched;
+  const uint32_t no_direct = (a.spatial == 1 && searched) ? 15u : una;
   const int dbias = no_direct ? 0 : a.dbias * lambda;
   int mode = 0, best = no_direct ? kNoCost : c_direct - dbias;  // 0 direct, 1 L0, 2 L1, 3 Bi
   if (c_l0 < best) { mode = 1; best = c_l0; }
@@ -1068,9 +1113,10 @@ using namespace mivc::gpu;
 
 extern "C" void mivc_launch_b_direct(int B, int wmb, int hmb, const void* col, const int* dsf, const int* direct_copy,
                                      int nref, int16_t* dmv, int8_t* dref, int16_t* pm0, int16_t* pm1, void* stream,
-                                     const void* route, int nbuf, uint8_t* czero) {
+                                     const void* route, int nbuf, uint8_t* czero, const int8_t* cmap) {
   BDirectArgs a;
   a.czero = czero;
+  a.cmap = cmap;
   a.rt = static_cast<const SlotRoute*>(route);
   a.nbuf = nbuf;
   a.g = Geom{B, wmb, hmb, wmb * 16, hmb * 16};

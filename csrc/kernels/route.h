@@ -54,5 +54,24 @@ inline size_t route_index(const SlotRoute* rt, int nbuf, int slot, int role) {
   return static_cast<size_t>(slot) * nbuf + (b < 0 ? 0 : b);
 }
 
+// MapColToList0 of temporal direct prediction (8.4.1.2.3), a [B][2][4] int8 table per coding
+// step beside the route rows (models/gop.py col_to_list0; only b_direct_mv reads it, and the
+// SlotRoute row stays 32 bytes).  The co-located block's reference -- refIdxCol r of the
+// co-located picture's list l (1: a reference B's list-1-only block) -- is
+// RefPicList0[r + cmap[slot][l][r]] of the slot's picture, or in none of its entries (kColNone).
+// Stored as an offset so that a zero table, like no table, is the identity: without a pyramid
+// both lists order the same past anchors.
+constexpr int8_t kColNone = -128;
+
+// -> refIdxL0, or -1 when the slot's list 0 does not hold the co-located reference
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int col_to_list0(const int8_t* cmap, int slot, int l, int r) {
+  if (!cmap) return r;
+  const int d = cmap[slot * 8 + (l & 1) * 4 + (r & 3)];
+  return d == kColNone ? -1 : (r + d) & 3;
+}
+
 }  // namespace gpu
 }  // namespace mivc

@@ -95,7 +95,11 @@ class EncoderConfig:
         bad = sorted(k for k in over if k not in fields)
         if bad:
             raise FfArgsError(f"{type(params).__name__} has no knob(s) {', '.join(bad)}")
-        if "direct" in fields:  # H.264: b-pyramid needs spatial direct prediction here
+        # H.264: the argument front keeps b-pyramid with spatial direct.  The encoder itself also
+        # runs it with temporal direct (H264Params(pyramid=True, direct="temporal")), but B pictures
+        # before the reference B then lose the direct prediction of blocks it predicted from
+        # list 1 alone (profiles/temporal_direct_pyramid.md), so no preset or argument selects it
+        if "direct" in fields:
             if over.get("pyramid") and over.get("direct", "spatial") != "spatial":
                 raise FfArgsError("b-pyramid needs direct=spatial with this encoder")
             if over.get("pyramid") and "direct" not in over:
@@ -205,8 +209,8 @@ H264_PARAMS = {
     # and ~26 % fewer frames/s than temporal on the benchmark content (profiles/r3_direct_rd.md)
     "direct": ("direct", _only("temporal", "spatial")),
     "b-adapt": ("@b-adapt", _only("0")),
-    # b-pyramid=normal: the middle B of a run is a reference; this encoder needs spatial direct
-    # for it (decided in the MB wavefront), so it implies direct=spatial (apply_opts)
+    # b-pyramid=normal: the middle B of a run is a reference; here it implies direct=spatial,
+    # decided in the MB wavefront (apply_opts; the encoder no longer needs spatial direct for it)
     "b-pyramid": ("pyramid", lambda v: _only("none", "normal")(v) == "normal"),
     "crf": ("@crf", _float_in(0.0, 51.0)),
     "qp": ("@qp", _int_in(0, 51)),

@@ -161,6 +161,30 @@ def h264_plan(types: str, refs: int = 1, pyramid: bool = False, nref_frames: int
     return out
 
 
+def col_to_list0(cur: PicPlan, col: PicPlan) -> tuple:
+    """MapColToList0 of temporal direct prediction (8.4.1.2.3) for the B picture ``cur`` whose
+    co-located picture (RefPicList1[0]) is ``col``: ``m[l][r]`` is the lowest index in
+    ``cur.refs0`` of the picture that ``col``'s list ``l`` names at refIdxCol ``r`` (``l`` 1: the
+    list-1 motion of a reference B's list-1-only block), or None when ``cur``'s list 0 does not
+    hold that picture -- such a block has no temporal direct prediction.  ``r`` runs to 4;
+    entries beyond ``col``'s list (no block carries them) are the identity.
+
+    Without a pyramid both lists order the same past anchors and the map is the identity.  With
+    one, a B picture after the run's reference B has that B in front of the anchors
+    (refIdxCol 0 -> refIdxL0 1), and a B picture before it takes the reference B as its
+    co-located picture, whose list 1 names the next anchor (not in list 0 here) and whose
+    list 0 may reach further back than the current one."""
+    def one(names: tuple) -> tuple:
+        out = []
+        for r in range(4):
+            if r < len(names):
+                out.append(cur.refs0.index(names[r]) if names[r] in cur.refs0 else None)
+            else:
+                out.append(r)
+        return tuple(out)
+    return one(col.refs0), one(col.refs1)
+
+
 def gop_plan(frames: int, bframes: int, anchors_at=(), refs: int = 1, pyramid: bool = False) -> list[PicPlan]:
     """Coding order of a closed GOP of ``frames`` pictures with x264's fixed --b-adapt 0
     pattern (:func:`fixed_types`, :func:`h264_plan`).

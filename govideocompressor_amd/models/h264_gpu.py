@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from ..ops import native
-from .gop import PicPlan, dpb_frames, fixed_types, gop_plan, h264_plan  # noqa: F401  (re-exported)
+from .gop import PicPlan, col_to_list0, dpb_frames, fixed_types, gop_plan, h264_plan  # noqa: F401  (re-exported)
 
 MB_HDR_BYTES = 64
 NO_COST = 0x3FFFFFFF  # me.hip kNoCost
@@ -34,6 +34,16 @@ ROUTE_DTYPE = np.dtype([("kind", "i1"), ("cur", "i1"), ("n0", "i1"), ("l1", "i1"
                         ("w1", "<i2", (4,)), ("dsf", "<i2", (4,)), ("dcopy", "i1", (4,)), ("flags", "u1"),
                         ("col_l1", "i1"), ("disp", "<i2")])
 assert ROUTE_DTYPE.itemsize == 32
+# route.h col_to_list0: MapColToList0 of temporal direct, [2, 4] int8 per slot and coding step
+# beside the route row, as offsets (refIdxL0 = r + cmap[l][r], COL_NONE: not in list 0) so
+# that zeros are the identity
+COL_NONE = -128
+
+
+def col_map_row(cur: PicPlan, col: PicPlan) -> np.ndarray:
+    """The [2, 4] int8 table of b_direct_mv for the B picture ``cur`` and its co-located picture."""
+    return np.array([[COL_NONE if m is None else m - r for r, m in enumerate(row)] for row in col_to_list0(cur, col)],
+                    dtype=np.int8)
 SK = {"P": 0, "B": 1, "I": 2}
 SF_REF, SF_DEBLOCK = 1, 2
 WP_LOG2 = 6  # luma / chroma log2 weight denominators of explicit weighted prediction
@@ -188,7 +198,10 @@ class H264Params:
     tdirect_bias: int = 8
     # x264 --b-pyramid normal: in a run of two or more B pictures the middle one is a reference
     # picture (coded first, predicted from the two anchors, then a reference of the others and of
-    # the next P); needs spatial direct (temporal direct's co-located motion would come from a B)
+    # the next P).  With temporal direct the co-located picture of the B pictures before it is
+    # that reference B: its blocks map into the current list 0 per slot (col_map_row), and
+    # those whose reference is not there (its list-1 motion points at the next anchor) have no
+    # direct prediction -- such MBs are searched and direct only in their other quadrants
     pyramid: bool = False
     trellis_lambda: float = 1.0
     # the same rate-distortion levels on the intra MBs' final encode (encode_intra.hip,
@@ -406,10 +419,6 @@ class GpuH264Encoder:
             raise ValueError("width and height must be even")
         if params.direct not in ("temporal", "spatial"):
             raise ValueError("direct must be 'temporal' or 'spatial'")
-        if params.eff_pyramid() and params.direct != "spatial":
-            # temporal direct scales the co-located block's motion by its own list-0 picture,
-            # which is the current list 0 only while RefPicList1[0] is a P anchor
-            raise ValueError("b-pyramid needs spatial direct prediction (direct='spatial')")
         if entropy not in ("gpu", "cpu"):
             raise ValueError("entropy must be 'gpu' or 'cpu'")
         if params.eff_slices() > 1 and params.direct == "spatial" and params.eff_bframes() and params.spatial_wavefront:
@@ -513,6 +522,13 @@ class GpuH264Encoder:
         self.far_ref_mbs = torch.zeros((), dtype=torch.int64, device=dev)  # P MBs choosing RefPicList0[1 ..]
         self.sfix_mbs = torch.zeros((), dtype=torch.int64, device=dev)  # fast spatial direct: MBs re-predicted
         self.sconv_mbs = torch.zeros((), dtype=torch.int64, device=dev)  # ... and MBs made explicit
+        # temporal direct under a pyramid: B MBs with a quadrant that has no direct prediction
+        self.una_mbs = torch.zeros((), dtype=torch.int64, device=dev)
+        self._una_count = bool(params.eff_pyramid() and params.direct == "temporal")
+        # set keep_records before encode(): last_records then holds, per coding step, copies of
+        # every slot's final MB records [B, nmb, 64] and of b_direct_mv's dref [B, nmb, 4] (tests)
+        self.keep_records = False
+        self.last_records = None
         # pinned staging for the entropy stage (double-buffered)
         if entropy == "cpu":
             self.h_hdr = [torch.empty((B, nmb, MB_HDR_BYTES), dtype=u8).pin_memory() for _ in range(2)]
@@ -787,7 +803,9 @@ class GpuH264Encoder:
             dbias = int(self.p.tdirect_bias) if not spatial else (int(self.p.direct_bias) if sfast else 0)
             with stt("me_b"):
                 self.hip.b_direct(B, wmb, hmb, P(self.col_pool), [0], [1], P(self.dmv), P(self.pm0), P(self.pm1), s,
-                                  P(self.dref), rt, NB, P(self.czero))
+                                  P(self.dref), rt, NB, P(self.czero), st["cmap"])
+                if self._una_count:
+                    self.una_mbs += ((self.dref < 0).any(dim=2) & st["bmask"][:, None]).sum()
                 if bg != 0 or sfast:  # direct costs first: MBs that direct already predicts well are not searched
                     self.hip.b_decide(B, wmb, hmb, sy, py, py, hpp, hpp, P(self.mv), P(self.mv1), P(self.me_cost),
                                       P(self.me_cost1), P(self.pred), P(self.pred1), P(self.pm0), P(self.pm1),
@@ -923,6 +941,9 @@ class GpuH264Encoder:
         sscale = np.zeros((F, 2, B), dtype=np.float32)
         deblock_nonref = bool(self._full_recon)
         col = {}
+        # MapColToList0 per B slot and step (spatial direct reads refIdxCol itself: no table)
+        use_cmap = self.p.direct == "temporal"
+        cmap = np.zeros((F, B, 2, 4), dtype=np.int8)
         colcache: dict[int, tuple] = {}  # one routing column per distinct plan (slots share plans)
         for b in range(B):
             key = id(plans[b])
@@ -934,7 +955,9 @@ class GpuH264Encoder:
                 c["dcopy"] = 1
                 xs = np.zeros((F, K), dtype=np.float32)
                 ss = np.zeros((F, 2), dtype=np.float32)
+                cm = np.zeros((F, 2, 4), dtype=np.int8)
                 kinds = {pic.d: pic.kind for pic in plans[b]}
+                by_d = {pic.d: pic for pic in plans[b]}
                 refs_at = []
                 for t, pic in enumerate(plans[b]):
                     r = c[t]
@@ -956,6 +979,8 @@ class GpuH264Encoder:
                     elif pic.kind == "B":
                         r["l1"] = pic.buf1
                         r["col_l1"] = int(kinds[pic.l1] == "B")
+                        if use_cmap:
+                            cm[t] = col_map_row(pic, by_d[pic.l1])
                         for k, rd in enumerate(pic.refs0):
                             dsf, copy = self._dist_scale(pic.poc, 2 * rd, 2 * pic.l1)
                             r["dsf"][k] = dsf
@@ -963,19 +988,24 @@ class GpuH264Encoder:
                             r["w1"][k] = dsf >> 2 if self.p.weightb and not copy and -64 <= (dsf >> 2) <= 128 else 32
                     if pic.ref and pic.kind != "I":
                         refs_at.append((t, pic.buf))
-                colcache[key] = (c, xs, refs_at, ss)
-            c, xs, refs_at, ss = colcache[key]
+                colcache[key] = (c, xs, refs_at, ss, cm)
+            c, xs, refs_at, ss, cm = colcache[key]
             rt[:, b] = c
+            cmap[:, b] = cm
             xscale[:, :, b] = xs
             sscale[:, :, b] = ss
             for t, buf in refs_at:
                 col.setdefault(t, []).append((b, b * NB + buf))
-        rt_d = torch.from_numpy(rt.view(np.uint8).reshape(F, B * 32).copy()).to(dev)
+        rt_d = torch.from_numpy(rt.view(np.uint8).reshape(F, B * ROUTE_DTYPE.itemsize).copy()).to(dev)
         kinds_d = torch.from_numpy(np.ascontiguousarray(rt["kind"])).to(dev)
         xs_d = torch.from_numpy(xscale).to(dev)
         ss_d = torch.from_numpy(sscale).to(dev)
+        # (all zero -- no pyramid -- is the identity: no table, b_direct_mv's plain path)
+        cmap_d = torch.from_numpy(cmap).to(dev) if cmap.any() else None
         self._route_dev = rt_d  # keeps the table alive while the launches read it
+        self._cmap_dev = cmap_d
         pmask_d = kinds_d == 0
+        bmask_d = kinds_d == 1
         # the co-located motion copies of every reference step: one upload, sliced per step (a
         # pair of small uploads per step cost ~1 ms of host latency each between two batches)
         cts = sorted(col)
@@ -989,8 +1019,9 @@ class GpuH264Encoder:
         for t in range(F):
             k = rt["kind"][t]
             n0p = rt["n0"][t][k == 0]
-            st = dict(route=rt_d[t].data_ptr(), P=bool((k == 0).any()), B=bool((k == 1).any()),
-                      pmask=pmask_d[t], maxn0=int(n0p.max()) if n0p.size else 1, xscale=xs_d[t],
+            st = dict(route=rt_d[t].data_ptr(), cmap=cmap_d[t].data_ptr() if cmap_d is not None else 0,
+                      P=bool((k == 0).any()), B=bool((k == 1).any()),
+                      pmask=pmask_d[t], bmask=bmask_d[t], maxn0=int(n0p.max()) if n0p.size else 1, xscale=xs_d[t],
                       deblock=bool((rt["flags"][t] & SF_DEBLOCK).any()), ref=bool((rt["flags"][t] & SF_REF).any()),
                       wp=None, wp_src=None, col_src=None, col_dst=None, kinds=k, sscale=ss_d[t])
             if t in cofs:
@@ -1580,6 +1611,7 @@ class GpuH264Encoder:
                 if group_futs[i].done() and group_futs[i].exception() is not None:
                     raise group_futs[i].exception()
         recons = None
+        records: list = []
         if keep_recon:
             recons = [tuple(torch.empty_like(p[:, 0]) for p in self.rec_pool) for _ in range(F)]
         main = torch.cuda.current_stream(self.dev)
@@ -1617,6 +1649,8 @@ class GpuH264Encoder:
                 self.hip.sse(B, self.W, self.H, self.p.width, self.p.height, P(self.src[0]), P(self.src[1]),
                              P(self.src[2]), P(self.rec_pool[0]), P(self.rec_pool[1]), P(self.rec_pool[2]),
                              sse[t].data_ptr(), ssim[t].data_ptr(), self._stream(), st["route"], self.nbuf)
+            if self.keep_records:
+                records.append((self.hdr[k].clone(), self.dref.clone()))
             if keep_recon:
                 bufs = torch.tensor([pic.buf for pic in pics], dtype=torch.long, device=self.dev)
                 slots = torch.arange(B, device=self.dev)
@@ -1666,12 +1700,14 @@ class GpuH264Encoder:
         # ---- end of the batch's issue: snapshot its counters (async) so the next batch can
         # reuse the accumulators, and note which groups last used the two CABAC rings
         B_ = B
-        counters = torch.stack([self.p_intra_mbs, self.far_ref_mbs, self.sfix_mbs, self.sconv_mbs]).to(torch.int64)
+        counters = torch.stack([self.p_intra_mbs, self.far_ref_mbs, self.sfix_mbs, self.sconv_mbs,
+                                self.una_mbs]).to(torch.int64)
         self.p_intra_mbs.zero_()
         self.far_ref_mbs.zero_()
         self.sfix_mbs.zero_()
         self.sconv_mbs.zero_()
-        h_counters = torch.empty((4,), dtype=torch.int64).pin_memory()
+        self.una_mbs.zero_()
+        h_counters = torch.empty((5,), dtype=torch.int64).pin_memory()
         h_counters.copy_(counters, non_blocking=True)
         h_sse = h_ssim = None
         if metrics:
@@ -1686,8 +1722,8 @@ class GpuH264Encoder:
                 a0, an = groups[gi]
                 self._ring_last[gi & 1] = (group_copied[gi], group_futs[gi], wrap_futs[a0:a0 + an])
         # tensors the in-flight kernels and copy threads still read (freed only after finish)
-        keep = (y, u, v, steps, qps_d, qps_ls_d, orders_d, cuts_d, self._route_dev, self._wp_steps, self._la_mv,
-                self._mbtree, sse, ssim, counters, analysis)
+        keep = (y, u, v, steps, qps_d, qps_ls_d, orders_d, cuts_d, self._route_dev, self._cmap_dev, self._wp_steps,
+                self._la_mv, self._mbtree, sse, ssim, counters, analysis)
         err_h = self.h_err[bno & 1]
 
         def finish() -> list[SegmentResult]:
@@ -1723,6 +1759,10 @@ class GpuH264Encoder:
                     # decoding-order pass changed after they were priced on the estimate / made explicit
                     self.stats["spatial_fix_ratio"] = float(c[2]) / (nbp * self.nmb)
                     self.stats["spatial_conv_ratio"] = float(c[3]) / (nbp * self.nmb)
+                if nbp and self._una_count:
+                    # temporal direct under a pyramid: share of B-picture MBs with a quadrant whose
+                    # co-located reference is not in list 0 (no B_Direct_16x16 / B_Skip there)
+                    self.stats["direct_unavail_ratio"] = float(c[4]) / (nbp * self.nmb)
             # the batch's error flags: with the GPU coder from its last group (copied behind the
             # coder on the entropy stream), else from the device after the batch's own work
             err = int(err_h[0]) if cabac_gpu else int(self.err_bufs[bno & 1].cpu()[0])
@@ -1753,6 +1793,8 @@ class GpuH264Encoder:
                 results.append(r)
             if keep_recon:
                 self.last_recon = recons
+            if self.keep_records:
+                self.last_records = records
             return results
 
         if defer and cabac_gpu:

@@ -83,6 +83,9 @@ CONFIGS = {
     # spatial direct decided exactly inside the MB wavefront (b_spatial_decide), + b-pyramid
     "sp_wave": dict(direct="spatial", spatial_wavefront=True),
     "sp_wave_pyr": dict(direct="spatial", spatial_wavefront=True, pyramid=True),
+    # b-pyramid with temporal direct (MapColToList0 per slot; blocks whose co-located reference
+    # is not in list 0 are searched): the pyramid without spatial direct's raster-order chain
+    "tdir_pyramid": dict(direct="temporal", pyramid=True),
     "i4p": dict(i4x4_in_p=True),  # x264's analysis: Intra4x4 trials in P / B pictures too
     "default": dict(),  # the current defaults
 }
@@ -155,7 +158,8 @@ def run(args):
                           ssim=float(np.mean([getattr(r, "ssim_y", 0.0) for r in res])), fps=args.slots * args.frames / dt,
                           b_ratio=stats.get("b_ratio", 0.0), scenecuts=stats.get("scenecuts", 0),
                           spatial_fix_ratio=stats.get("spatial_fix_ratio"),
-                          spatial_conv_ratio=stats.get("spatial_conv_ratio"))
+                          spatial_conv_ratio=stats.get("spatial_conv_ratio"),
+                          direct_unavail_ratio=stats.get("direct_unavail_ratio"))
                 out["points"].append(pt)
                 print(json.dumps(pt), flush=True)
         enc.close()
