@@ -7,8 +7,9 @@
 //   * 4x4 forward core transform, dead-zone quantisation, x264-style coefficient
 //     decimation, dequantisation and the normative inverse transform, so the
 //     reconstruction written here is exactly what a decoder produces.
-// SURVEY.md K-C8.  One wave64 per four macroblocks: luma on all 64 lanes (one 16-lane row
-// per MB, a lane per 4x4 block), then chroma on 32 lanes (see encode_inter_mb).
+// SURVEY.md K-C8.  Two launches, every lane of a wave64 at work in both: luma four macroblocks
+// per wave (one 16-lane row per MB, a lane per 4x4 block: encode_inter_mb), then chroma eight
+// per wave (eight lanes per MB: encode_inter_chroma).
 #include "h264_trellis.h"
 #include "mb_row.h"
 
@@ -74,38 +75,79 @@ __device__ __forceinline__ int wp_sample(int p, int w, int o, int d) {
 }
 
 
+// Chroma predictions travel as pairs of 16-bit samples: a 4x4 block is pp[4][2], pp[y][0] =
+// samples (x0, x1) of row y, pp[y][1] = (x2, x3).  The bilinear sum and the bi-prediction blend
+// fit 16 bits (the weights sum to 64, samples are <= 255: at most 64 * 255 + 32), so they run
+// two samples per instruction (v_pk_mul_lo_u16 / v_pk_mad_u16 / v_pk_lshrrev_b16).
+typedef unsigned short v2u16 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ v2u16 as_v2u16(uint32_t x) { return __builtin_bit_cast(v2u16, x); }
+__device__ __forceinline__ uint32_t as_u32(v2u16 x) { return __builtin_bit_cast(uint32_t, x); }
+__device__ __forceinline__ v2u16 splat_u16(int v) {
+  return v2u16{static_cast<unsigned short>(v), static_cast<unsigned short>(v)};
+}
+__device__ __forceinline__ int pair_lo(uint32_t p) { return static_cast<int>(p & 0xFFFFu); }
+__device__ __forceinline__ int pair_hi(uint32_t p) { return static_cast<int>(p >> 16); }
+__device__ __forceinline__ uint32_t make_pair(int lo, int hi) {  // both in [0, 65535]
+  return static_cast<uint32_t>(lo) | (static_cast<uint32_t>(hi) << 16);
+}
+// the four samples of a row of pairs (each <= 255) as one little-endian word
+__device__ __forceinline__ uint32_t pairs_to_u8x4(const uint32_t (&p)[2]) {
+  return __builtin_amdgcn_perm(p[1], p[0], 0x06040200u);
+}
+
 // Eighth-sample chroma prediction (clause 8.4.2.2.2) of a 4x4 block at (px0, py0) of a
-// cw x ch plane with vector (mvx, mvy) (quarter-luma = eighth-chroma units).
+// cw x ch plane with vector (mvx, mvy) (quarter-luma = eighth-chroma units), as pairs.
 __device__ __forceinline__ void chroma_mc4x4(const uint8_t* refc, int cw, int CH, int px0, int py0, int mvx, int mvy,
-                                             int (&pv)[4][4]) {
+                                             uint32_t (&pp)[4][2]) {
   const int xf = mvx & 7, yf = mvy & 7;
   const int xi = px0 + (mvx >> 3), yi = py0 + (mvy >> 3);
-  int rw[5][5];  // reference samples (rows yi..yi+4, cols xi..xi+4), edge-clamped
+  // reference samples (rows yi..yi+4, cols xi..xi+4), edge-clamped, as the pairs the sum takes:
+  // ra[r] = (c0, c1), (c2, c3) and rb[r] = (c1, c2), (c3, c4)
+  uint32_t ra[5][2], rb[5][2];
   if (xi >= 0 && xi + 8 <= cw && yi >= 0 && yi + 5 <= CH) {
+    // bytes s .. s + 4 of an aligned dword pair (s = xi & 3), widened by v_perm (0x0c: zero)
+    const uint32_t s = static_cast<uint32_t>(xi & 3) * 0x00010001u;
+    const uint32_t sa0 = 0x0c010c00u + s, sa1 = 0x0c030c02u + s, sb0 = 0x0c020c01u + s, sb1 = 0x0c040c03u + s;
 #pragma unroll
     for (int r = 0; r < 5; ++r) {
       const uint8_t* row = refc + static_cast<size_t>(yi + r) * cw;
       const int a = xi & ~3;
       const uint32_t w0 = *reinterpret_cast<const uint32_t*>(row + a), w1 = *reinterpret_cast<const uint32_t*>(row + a + 4);
-      const uint32_t w4 = __builtin_amdgcn_alignbyte(w1, w0, xi & 3), w5 = row[xi + 4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) rw[r][c] = __builtin_amdgcn_ubfe(w4, 8 * c, 8);
-      rw[r][4] = w5;
+      ra[r][0] = __builtin_amdgcn_perm(w1, w0, sa0);
+      ra[r][1] = __builtin_amdgcn_perm(w1, w0, sa1);
+      rb[r][0] = __builtin_amdgcn_perm(w1, w0, sb0);
+      rb[r][1] = __builtin_amdgcn_perm(w1, w0, sb1);
     }
   } else {
 #pragma unroll
     for (int r = 0; r < 5; ++r) {
       const uint8_t* row = refc + static_cast<size_t>(clampi(yi + r, 0, CH - 1)) * cw;
+      int c[5];
 #pragma unroll
-      for (int c = 0; c < 5; ++c) rw[r][c] = row[clampi(xi + c, 0, cw - 1)];
+      for (int i = 0; i < 5; ++i) c[i] = row[clampi(xi + i, 0, cw - 1)];
+      ra[r][0] = make_pair(c[0], c[1]);
+      ra[r][1] = make_pair(c[2], c[3]);
+      rb[r][0] = make_pair(c[1], c[2]);
+      rb[r][1] = make_pair(c[3], c[4]);
     }
   }
-  const int wA = (8 - xf) * (8 - yf), wB = xf * (8 - yf), wC = (8 - xf) * yf, wD = xf * yf;
+  const v2u16 wA = splat_u16((8 - xf) * (8 - yf)), wB = splat_u16(xf * (8 - yf)), wC = splat_u16((8 - xf) * yf),
+              wD = splat_u16(xf * yf), half = splat_u16(32);
 #pragma unroll
   for (int y = 0; y < 4; ++y)
 #pragma unroll
-    for (int x = 0; x < 4; ++x)
-      pv[y][x] = (wA * rw[y][x] + wB * rw[y][x + 1] + wC * rw[y + 1][x] + wD * rw[y + 1][x + 1] + 32) >> 6;
+    for (int h = 0; h < 2; ++h)
+      pp[y][h] = as_u32((half + wA * as_v2u16(ra[y][h]) + wB * as_v2u16(rb[y][h]) + wC * as_v2u16(ra[y + 1][h]) +
+                         wD * as_v2u16(rb[y + 1][h])) >> 6);
+}
+
+// 16 levels to a 16-byte aligned row of the coefficient buffer
+__device__ __forceinline__ void store_levels(int16_t* dst, const int* v) {
+  uint32_t w[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) w[i] = (static_cast<uint32_t>(v[2 * i]) & 0xFFFFu) | (static_cast<uint32_t>(v[2 * i + 1]) << 16);
+  reinterpret_cast<uint4*>(dst)[0] = make_uint4(w[0], w[1], w[2], w[3]);
+  reinterpret_cast<uint4*>(dst)[1] = make_uint4(w[4], w[5], w[6], w[7]);
 }
 
 // x264 decimate_score of a 4x4 block in scan order (start..15), branch-free: 9 if any
@@ -135,24 +177,20 @@ __device__ __forceinline__ uint32_t ld4(const uint8_t* row, int x) {
   return __builtin_amdgcn_alignbyte(w1, w0, x & 3);
 }
 
-// Four macroblocks per wave64, one 16-lane row each (MB 4i + q on lanes 16q .. 16q + 15), in
-// two phases so that every instruction runs for as many lanes as the work has:
-//   1. luma on all 64 lanes (lane l of a row = luma4x4BlkIdx l), from the 4x4 transform to the
-//      reconstruction store: quantisation / trellis, decimation, the 8x8 trial (sa8d of the
-//      16 8x8 blocks of the wave on the int8 matrix cores, one MFMA column each) and its
-//      decision, final levels, inverse transform.  Lane 0 of each row writes the MB record.
-//   2. chroma on lanes 0-31 (MB lane >> 3, component (lane >> 2) & 1, 4x4 block lane & 3):
-//      motion compensation, transform, the 2x2 DC Hadamard, levels, reconstruction.
-// Luma decisions never depend on chroma, so no luma state (levels, prediction rows) is live
-// while chroma runs: the register need is the larger of the two phases, not their sum.
+// Luma: four macroblocks per wave64, one 16-lane row each (MB 4i + q on lanes 16q .. 16q + 15,
+// lane l of a row = luma4x4BlkIdx l), from the 4x4 transform to the reconstruction store:
+// quantisation / trellis, decimation, the 8x8 trial (sa8d of the 16 8x8 blocks of the wave on
+// the int8 matrix cores, one MFMA column each) and its decision, final levels, inverse
+// transform.  Lane 0 of each row writes the MB record.  Chroma is encode_inter_chroma's: luma
+// decisions never depend on it, and eight MBs' chroma fill a wave where four MBs' fill half.
 // Block sums, masks and minima stay in registers: a 4x4 block's 8x8 block is its lane quad,
-// its MB its DPP row, so the decimation scores, the 8x8 statistics, the chroma DC and the
-// keep masks are quad / row DPP reductions.  LDS holds only what crosses lanes irregularly:
+// its MB its DPP row, so the decimation scores, the 8x8 statistics and the keep masks are
+// quad / row DPP reductions.  LDS holds only what crosses lanes irregularly:
 // the packed samples of the sa8d operands (2 KiB) and the 8x8 transform buffers (4 KiB).
 // With 6 KiB of LDS per wave and at most 128 VGPRs, 16 single-wave blocks still fit a CU
 // (160 KiB LDS, 512 VGPRs per SIMD lane): four waves per SIMD as before
 // (profiles/r5_occupancy_ab.md, profiles/inter_four_mb_per_wave.md).
-// Rows move as dwords (prediction, source, reference, reconstruction), levels as 16-byte
+// Rows move as dwords (prediction, source, reconstruction), levels as 16-byte
 // stores, and the decimation score is branch-free.  Every wave_sync() sits in wave-uniform
 // control flow; MBs of a wave that are dead (tail), intra-flagged or not on the 8x8 path are
 // masked by per-lane predicates, never by an early exit.
@@ -164,54 +202,36 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
   xcd_unit_slot(ux, slot);
   if (!route_active(a.rt, slot, a.bmode ? SK_B : SK_P)) return;  // wave-uniform
   const size_t rcur = route_index(a.rt, a.nbuf, slot, RO_CUR);
-  const int W = g.W, cw = g.cw(), CH = g.ch();
-  // the wave's first MB (always inside the picture); MB qi follows it in raster order
-  const int mb0 = ux * kMbsPerWave, mx0 = mb0 % g.wmb, my0 = mb0 / g.wmb;
-  // MB qi of the wave (the tail's dead lanes are clamped to the last MB): position, record
-  // index, inter-coded here (work), QP.  With adaptive quantisation the four MBs have four
-  // QPs: every lane fetches its own MB's table rows (one address, 3-dword loads) -- fewer
-  // registers and instructions than four scalar rows and three-deep selects per value.
-  auto locate = [&](int qi, int& mx, int& my, size_t& o, bool& work, int& qp) {
-    const bool live = mb0 + qi < nmb;
-    const int d = live ? qi : nmb - 1 - mb0;  // 0..3
-    mx = mx0 + d;
-    my = my0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {  // at most 3 row wraps (wmb = 1)
-      const bool wrap = mx >= g.wmb;
-      mx -= wrap ? g.wmb : 0;
-      my += wrap ? 1 : 0;
-    }
-    o = static_cast<size_t>(slot) * nmb + mb0 + d;
-    work = live && !(a.intra_cost[o] < a.me_cost[o]);
-    qp = clampi(a.qp[slot] + (a.aq ? a.aq[o] : 0), 0, 51);
-    return live;
-  };
+  const int W = g.W;
+  // the wave's first MB (always inside the picture); MB q follows it in raster order
+  const int mb0 = ux * kMbsPerWave;
 
   // 8x8 transform path (a.t8): the luma source / prediction samples (sa8d operands) and the
   // 8x8 transform buffers (residual -> coefficients, later dequantised levels -> residual)
   __shared__ uint32_t s_px[kMbsPerWave][2][16][4];  // [MB][source / prediction][row][dword]
   __shared__ int s_d8[kMbsPerWave][4][64];          // [MB][8x8 block][raster]
 
-  auto store_levels = [](int16_t* dst, const int* v) {  // 16 levels, 16-byte aligned
-    uint32_t w[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) w[i] = (static_cast<uint32_t>(v[2 * i]) & 0xFFFFu) | (static_cast<uint32_t>(v[2 * i + 1]) << 16);
-    reinterpret_cast<uint4*>(dst)[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    reinterpret_cast<uint4*>(dst)[1] = make_uint4(w[4], w[5], w[6], w[7]);
-  };
-
   int lv[16];       // levels of this lane's block (raster; scan order of its chunk on the 8x8 path)
   int res[16];      // residual / reconstruction scratch
   uint32_t prw[4];  // prediction rows (4 bytes each)
-  uint64_t luma_any = 0;  // lanes whose luma block has a level (a 16-lane row per MB): for a.qp_flags
 
-  // ================================================================ phase 1: luma
   {
-    int mx, my, qp;
-    size_t o;
-    bool work;
-    const bool live = locate(q, mx, my, o, work, qp);
+    // this row's MB (the tail's dead rows are clamped to the last MB): position, record index,
+    // inter-coded here (work), QP.  With adaptive quantisation the four MBs have four QPs:
+    // every lane fetches its own MB's table rows (one address, 3-dword loads) -- fewer
+    // registers and instructions than four scalar rows and three-deep selects per value.
+    const bool live = mb0 + q < nmb;
+    const int d = live ? q : nmb - 1 - mb0;  // 0..3
+    int mx = mb0 % g.wmb + d, my = mb0 / g.wmb;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {  // at most 3 row wraps (wmb = 1)
+      const bool wrap = mx >= g.wmb;
+      mx -= wrap ? g.wmb : 0;
+      my += wrap ? 1 : 0;
+    }
+    const size_t o = static_cast<size_t>(slot) * nmb + mb0 + d;
+    const bool work = live && !(a.intra_cost[o] < a.me_cost[o]);
+    const int qp = clampi(a.qp[slot] + (a.aq ? a.aq[o] : 0), 0, 51);
     MbHeader* h = a.hdr + o;
     int16_t* coef = a.coef + o * h264::kCoefPerMb;
     if (live && !work && l == 0) {
@@ -482,7 +502,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
       if (any) h264::inverse_core4x4(res);
     }
     const bool t8_coded = ((__ballot(keep8) >> (16 * q)) & 0xFFFFu) != 0;  // the MB has 8x8 levels
-    luma_any = __ballot(any);  // (`any` is false outside `work`)
+    if (a.qp_flags) {
+      // the MB's byte from luma alone (`any` is false outside `work`); encode_inter_chroma,
+      // next on the stream, raises it to 1 for an MB that has chroma levels only
+      const uint64_t luma_any = __ballot(any);
+      if (live && l == 0) a.qp_flags[o] = !work ? 2 : (((luma_any >> (16 * q)) & 0xFFFFu) != 0 ? 1 : 0);
+    }
     if (work) {
       uint8_t* recy = a.rec_y + rcur * g.ysize() + static_cast<size_t>(Y0 + lby) * W + X0 + lbx;
 #pragma unroll
@@ -521,140 +546,183 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
     }
   }
 
-  // ================================================================ phase 2: chroma
-  {
-    // lanes 0-31: MB lane >> 3, component comp, 4x4 block cb (a quad = one component of one MB)
-    const int comp = (lane >> 2) & 1, cb = lane & 3;
-    int mx, my, qpy;
-    size_t o;
-    bool work;
-    const bool live = locate((lane >> 3) & 3, mx, my, o, work, qpy);
-    work = work && lane < 32;
-    const MbHeader* h = a.hdr + o;
-    int16_t* coef = a.coef + o * h264::kCoefPerMb;
-    const int qpc = h264::chroma_qp(qpy, a.chroma_qp_offset);
-    const int cbx = (cb & 1) * 4, cby = (cb >> 1) * 4;
-    int mfc[3], dvc[3];
-    int dc = 0, score = 0;
-    if (work) {
-      // ---- eighth-sample MC (clause 8.4.2.2.2) + residual + forward + AC quantisation
+}
+
+// Chroma of the same MBs: eight per wave64 (MB 8i + m on lanes 8m .. 8m + 7: component
+// comp = (lane >> 2) & 1, 4x4 block cb = lane & 3, so a quad is one component of one MB): motion
+// compensation, transform, the 2x2 DC Hadamard, levels, reconstruction.  It takes nothing from
+// encode_inter_mb but the stream order: which MBs are coded here, their vectors, references and
+// QP come from the same inputs (P pictures: mv / mv8 / mref; B pictures: b_decide's records).
+// The component's four DC terms and its AC decimation score are quad DPP reductions, formed
+// by every lane before they are tested; dead MBs of the last wave are clamped to the last MB
+// and masked, never left early.  No LDS.
+__global__ __launch_bounds__(64) void encode_inter_chroma(InterArgs a) {
+  const Geom& g = a.g;
+  const int lane = threadIdx.x, m = lane >> 3, comp = (lane >> 2) & 1, cb = lane & 3;
+  const int nmb = g.nmb();
+  int ux, slot;
+  xcd_unit_slot(ux, slot);
+  if (!route_active(a.rt, slot, a.bmode ? SK_B : SK_P)) return;  // wave-uniform
+  const size_t rcur = route_index(a.rt, a.nbuf, slot, RO_CUR);
+  const int cw = g.cw(), CH = g.ch();
+  const int mb0 = ux * kMbsPerChromaWave;  // always inside the picture
+  const bool live = mb0 + m < nmb;
+  const int dm = live ? m : nmb - 1 - mb0;  // 0..7
+  int mx = mb0 % g.wmb + dm, my = mb0 / g.wmb;
+  while (__ballot(mx >= g.wmb)) {  // row wraps: one at most unless the picture is under 8 MBs wide
+    const bool wrap = mx >= g.wmb;
+    mx -= wrap ? g.wmb : 0;
+    my += wrap ? 1 : 0;
+  }
+  const size_t o = static_cast<size_t>(slot) * nmb + mb0 + dm;
+  const bool work = live && !(a.intra_cost[o] < a.me_cost[o]);
+  const int qpc = h264::chroma_qp(clampi(a.qp[slot] + (a.aq ? a.aq[o] : 0), 0, 51), a.chroma_qp_offset);
+  const MbHeader* h = a.hdr + o;
+  int16_t* coef = a.coef + o * h264::kCoefPerMb;
+  const int cbx = (cb & 1) * 4, cby = (cb >> 1) * 4;
+
+  int lv[16];       // AC levels of this lane's block (raster)
+  int res[16];      // residual / reconstruction scratch
+  uint32_t prw[4];  // prediction rows (4 bytes each)
+  int mfc[3], dvc[3];
+  int dc = 0, score = 0;
+  if (work) {
+    // ---- eighth-sample MC (clause 8.4.2.2.2) + residual + forward + AC quantisation
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        mfc[c] = h264::kQuantMF[qpc % 6][c];
-        dvc[c] = h264::kDequantV[qpc % 6][c];
-      }
-      const uint8_t* srcc = (comp == 0 ? a.src_u : a.src_v) + slot * g.csize();
-      const int px0 = mx * 8 + cbx, py0 = my * 8 + cby;
-      int pv[4][4];
-      if (!a.bmode) {
-        // the 4x4 chroma block cb covers luma quadrant cb (its partition's vector)
-        const int cmx = a.mv8 ? a.mv8[o * 8 + cb * 2] : a.mv[o * 2], cmy = a.mv8 ? a.mv8[o * 8 + cb * 2 + 1] : a.mv[o * 2 + 1];
-        const int r = a.mref ? a.mref[o] : 0;
-        chroma_mc4x4((comp == 0 ? a.refs_u[r] : a.refs_v[r]) + route_index(a.rt, a.nbuf, slot, RO_L0 + r) * g.csize(), cw,
-                     CH, px0, py0, cmx, cmy, pv);
-        if (a.wp && r == 0) {
-          const int* wt = a.wp + slot * 8;
-          const int w = wt[3 + 2 * comp], wo = wt[4 + 2 * comp], d = wt[7];
-          if (w != (1 << d) || wo != 0) {
+    for (int c = 0; c < 3; ++c) {
+      mfc[c] = h264::kQuantMF[qpc % 6][c];
+      dvc[c] = h264::kDequantV[qpc % 6][c];
+    }
+    const uint8_t* srcc = (comp == 0 ? a.src_u : a.src_v) + slot * g.csize();
+    const int px0 = mx * 8 + cbx, py0 = my * 8 + cby;
+    uint32_t pp[4][2];
+    if (!a.bmode) {
+      // the 4x4 chroma block cb covers luma quadrant cb (its partition's vector)
+      const int cmx = a.mv8 ? a.mv8[o * 8 + cb * 2] : a.mv[o * 2], cmy = a.mv8 ? a.mv8[o * 8 + cb * 2 + 1] : a.mv[o * 2 + 1];
+      const int r = a.mref ? a.mref[o] : 0;
+      chroma_mc4x4((comp == 0 ? a.refs_u[r] : a.refs_v[r]) + route_index(a.rt, a.nbuf, slot, RO_L0 + r) * g.csize(), cw,
+                   CH, px0, py0, cmx, cmy, pp);
+      if (a.wp && r == 0) {
+        const int* wt = a.wp + slot * 8;
+        const int w = wt[3 + 2 * comp], wo = wt[4 + 2 * comp], d = wt[7];
+        if (w != (1 << d) || wo != 0) {
 #pragma unroll
-            for (int y = 0; y < 4; ++y)
+          for (int y = 0; y < 4; ++y)
 #pragma unroll
-              for (int x = 0; x < 4; ++x) pv[y][x] = wp_sample(pv[y][x], w, wo, d);
-          }
+            for (int hh = 0; hh < 2; ++hh)
+              pp[y][hh] = make_pair(wp_sample(pair_lo(pp[y][hh]), w, wo, d), wp_sample(pair_hi(pp[y][hh]), w, wo, d));
         }
-      } else {
-        // the 4x4 chroma block cb covers luma quadrant cb: its lists and vectors
-        const int r0 = h->ref[0][cb];
-        const bool u0 = r0 >= 0, u1 = h->ref[1][cb] >= 0;
-        const int w1 = a.rt ? a.rt[slot].w1[r0 & 3] : a.w1[r0 & 3];
-        int p1[4][4];
-        if (u0) chroma_mc4x4((comp == 0 ? a.refs_u[r0 & 3] : a.refs_v[r0 & 3]) +
-                                 route_index(a.rt, a.nbuf, slot, RO_L0 + (r0 & 3)) * g.csize(), cw, CH, px0, py0,
-                             h->mv[0][cb][0], h->mv[0][cb][1], pv);
-        if (u1) chroma_mc4x4((comp == 0 ? a.ref1_u : a.ref1_v) + route_index(a.rt, a.nbuf, slot, RO_L1) * g.csize(), cw,
-                             CH, px0, py0,
-                             h->mv[1][cb][0], h->mv[1][cb][1], p1);
+      }
+    } else {
+      // the 4x4 chroma block cb covers luma quadrant cb: its lists and vectors
+      const int r0 = h->ref[0][cb];
+      const bool u0 = r0 >= 0, u1 = h->ref[1][cb] >= 0;
+      const int w1 = a.rt ? a.rt[slot].w1[r0 & 3] : a.w1[r0 & 3];
+      uint32_t p1[4][2];
+      if (u0) chroma_mc4x4((comp == 0 ? a.refs_u[r0 & 3] : a.refs_v[r0 & 3]) +
+                               route_index(a.rt, a.nbuf, slot, RO_L0 + (r0 & 3)) * g.csize(), cw, CH, px0, py0,
+                           h->mv[0][cb][0], h->mv[0][cb][1], pp);
+      if (u1) chroma_mc4x4((comp == 0 ? a.ref1_u : a.ref1_v) + route_index(a.rt, a.nbuf, slot, RO_L1) * g.csize(), cw,
+                           CH, px0, py0,
+                           h->mv[1][cb][0], h->mv[1][cb][1], p1);
+      // implicit weights (w1 = 32: the plain average).  With both weights in [0, 64] the sum
+      // fits 16 bits and needs no clip, so it runs on pairs; a weight outside (the lists on one
+      // side of the picture) takes the 32-bit form.  Wave-uniform: one form per wave.
+      const bool bi = u0 && u1;
+      if (__ballot(bi && (w1 < 0 || w1 > 64)) == 0) {
+        const v2u16 k0 = splat_u16(64 - w1), k1 = splat_u16(w1), half = splat_u16(32);
 #pragma unroll
         for (int y = 0; y < 4; ++y)
 #pragma unroll
-          for (int x = 0; x < 4; ++x)  // implicit weights (a.w1 = 32: the plain average)
-            pv[y][x] = u0 ? (u1 ? h264::clip1((pv[y][x] * (64 - w1) + p1[y][x] * w1 + 32) >> 6) : pv[y][x]) : p1[y][x];
-      }
-      uint32_t sw[4];
-#pragma unroll
-      for (int y = 0; y < 4; ++y) sw[y] = *reinterpret_cast<const uint32_t*>(srcc + static_cast<size_t>(py0 + y) * cw + px0);
-#pragma unroll
-      for (int y = 0; y < 4; ++y) {
-#pragma unroll
-        for (int x = 0; x < 4; ++x) res[y * 4 + x] = static_cast<int>(__builtin_amdgcn_ubfe(sw[y], 8 * x, 8)) - pv[y][x];
-        prw[y] = pack4_u8(pv[y]);
-      }
-      h264::forward_core4x4(res);
-      dc = res[0];
-      const int qbits = 15 + qpc / 6;
-      if (a.trellis >= 2) {  // chroma AC by the same rate-distortion choice, at the chroma QP's lambda
-        trellis_lite4x4(res, lv, mfc, qbits, trellis_lambda4(a.trellis_lambda, qpc), 1);
+          for (int hh = 0; hh < 2; ++hh) {
+            const uint32_t b2 = as_u32((half + as_v2u16(pp[y][hh]) * k0 + as_v2u16(p1[y][hh]) * k1) >> 6);
+            pp[y][hh] = u0 ? (u1 ? b2 : pp[y][hh]) : p1[y][hh];
+          }
       } else {
 #pragma unroll
-        for (int r = 0; r < 16; ++r)
-          lv[r] = r == 0 ? 0 : h264::quant_coef(res[r], mfc[h264::kPosClass[r]], qbits, 11);
-      }
-      int scan[16];
+        for (int y = 0; y < 4; ++y)
 #pragma unroll
-      for (int i = 0; i < 16; ++i) scan[i] = lv[h264::kZigzag4x4[i]];
-      score = decimate_score(scan, 1);
-    }
-    // the component's four DC terms and its AC decimation score live in the quad
-    const int d0 = quad_bcast<0>(dc), d1 = quad_bcast<1>(dc), d2 = quad_bcast<2>(dc), d3 = quad_bcast<3>(dc);
-    const int score_c = sum4(score);
-    const bool keep_ac = score_c >= 7;
-    bool any_c = false;  // this block has an AC level or its component a DC level
-    if (work) {
-      // chroma DC: 2x2 Hadamard + quantisation with qbits+1 (every lane of the quad: no hand-off)
-      const int f[4] = {d0 + d1 + d2 + d3, d0 - d1 + d2 - d3, d0 + d1 - d2 - d3, d0 - d1 - d2 + d3};
-      int cl[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) cl[i] = h264::quant_coef(f[i], mfc[0], 15 + qpc / 6 + 1, 11);
-      int sv[16];
-      bool any_ac = false;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        sv[i] = (keep_ac && i > 0) ? lv[h264::kZigzag4x4[i]] : 0;
-        any_ac |= sv[i] != 0;
-      }
-      store_levels(coef + h264::COEF_CHROMA_AC + (comp * 4 + cb) * 16, sv);
-      if (cb == 0) {
-        // chroma DC levels (Cb then Cr, 4 x int16 each at COEF_CHROMA_DC)
-        auto p2 = [](int lo, int hi) { return (static_cast<uint32_t>(lo) & 0xFFFFu) | (static_cast<uint32_t>(hi) << 16); };
-        *reinterpret_cast<uint2*>(coef + h264::COEF_CHROMA_DC + comp * 4) = make_uint2(p2(cl[0], cl[1]), p2(cl[2], cl[3]));
-      }
-      // this block's row of the 2x2 Hadamard (signs by cb: no dynamically indexed array)
-      const int c0 = cl[0], c1 = cl[1], c2 = cl[2], c3 = cl[3];
-      const int fcb = cb == 0 ? c0 + c1 + c2 + c3 : (cb == 1 ? c0 - c1 + c2 - c3 : (cb == 2 ? c0 + c1 - c2 - c3 : c0 - c1 - c2 + c3));
-      const int ls = 16 * dvc[0];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) res[r] = (keep_ac && r > 0) ? (lv[r] * dvc[h264::kPosClass[r]]) << (qpc / 6) : 0;
-      res[0] = ((fcb * ls) << (qpc / 6)) >> 5;
-      const bool any = any_ac || c0 || c1 || c2 || c3;
-      any_c = any;
-      if (any) h264::inverse_core4x4(res);
-      uint8_t* recc = (comp == 0 ? a.rec_u : a.rec_v) + rcur * g.csize() + static_cast<size_t>(my * 8 + cby) * cw + mx * 8 + cbx;
-#pragma unroll
-      for (int y = 0; y < 4; ++y) {
-        int v4[4];
-#pragma unroll
-        for (int x = 0; x < 4; ++x)
-          v4[x] = h264::clip1(static_cast<int>(__builtin_amdgcn_ubfe(prw[y], 8 * x, 8)) + (any ? res[y * 4 + x] : 0));
-        *reinterpret_cast<uint32_t*>(recc + static_cast<size_t>(y) * cw) = pack4_u8(v4);
+          for (int hh = 0; hh < 2; ++hh) {
+            const int lo = h264::clip1((pair_lo(pp[y][hh]) * (64 - w1) + pair_lo(p1[y][hh]) * w1 + 32) >> 6);
+            const int hi = h264::clip1((pair_hi(pp[y][hh]) * (64 - w1) + pair_hi(p1[y][hh]) * w1 + 32) >> 6);
+            pp[y][hh] = u0 ? (u1 ? make_pair(lo, hi) : pp[y][hh]) : p1[y][hh];
+          }
       }
     }
-    if (a.qp_flags) {
-      // MB m of the wave: luma on lanes 16 m .. 16 m + 15 of phase 1, chroma on lanes 8 m .. 8 m + 7
-      const uint64_t chroma_any = __ballot(any_c);
-      const int m = (lane >> 3) & 3;
-      if (live && lane < 32 && (lane & 7) == 0)
-        a.qp_flags[o] = !work ? 2 : ((((luma_any >> (16 * m)) & 0xFFFFu) | ((chroma_any >> (8 * m)) & 0xFFu)) != 0 ? 1 : 0);
+    uint32_t sw[4];
+#pragma unroll
+    for (int y = 0; y < 4; ++y) sw[y] = *reinterpret_cast<const uint32_t*>(srcc + static_cast<size_t>(py0 + y) * cw + px0);
+#pragma unroll
+    for (int y = 0; y < 4; ++y) {
+#pragma unroll
+      for (int x = 0; x < 4; ++x)
+        res[y * 4 + x] = static_cast<int>(__builtin_amdgcn_ubfe(sw[y], 8 * x, 8)) -
+                         ((x & 1) ? pair_hi(pp[y][x >> 1]) : pair_lo(pp[y][x >> 1]));
+      prw[y] = pairs_to_u8x4(pp[y]);
     }
+    h264::forward_core4x4(res);
+    dc = res[0];
+    const int qbits = 15 + qpc / 6;
+    if (a.trellis >= 2) {  // chroma AC by the same rate-distortion choice, at the chroma QP's lambda
+      trellis_lite4x4(res, lv, mfc, qbits, trellis_lambda4(a.trellis_lambda, qpc), 1);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        lv[r] = r == 0 ? 0 : h264::quant_coef(res[r], mfc[h264::kPosClass[r]], qbits, 11);
+    }
+    int scan[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) scan[i] = lv[h264::kZigzag4x4[i]];
+    score = decimate_score(scan, 1);
+  }
+  // the component's four DC terms and its AC decimation score live in the quad
+  const int d0 = quad_bcast<0>(dc), d1 = quad_bcast<1>(dc), d2 = quad_bcast<2>(dc), d3 = quad_bcast<3>(dc);
+  const int score_c = sum4(score);
+  const bool keep_ac = score_c >= 7;
+  bool any_c = false;  // this block has an AC level or its component a DC level
+  if (work) {
+    // chroma DC: 2x2 Hadamard + quantisation with qbits+1 (every lane of the quad: no hand-off)
+    const int f[4] = {d0 + d1 + d2 + d3, d0 - d1 + d2 - d3, d0 + d1 - d2 - d3, d0 - d1 - d2 + d3};
+    int cl[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) cl[i] = h264::quant_coef(f[i], mfc[0], 15 + qpc / 6 + 1, 11);
+    int sv[16];
+    bool any_ac = false;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      sv[i] = (keep_ac && i > 0) ? lv[h264::kZigzag4x4[i]] : 0;
+      any_ac |= sv[i] != 0;
+    }
+    store_levels(coef + h264::COEF_CHROMA_AC + (comp * 4 + cb) * 16, sv);
+    if (cb == 0) {
+      // chroma DC levels (Cb then Cr, 4 x int16 each at COEF_CHROMA_DC)
+      auto p2 = [](int lo, int hi) { return (static_cast<uint32_t>(lo) & 0xFFFFu) | (static_cast<uint32_t>(hi) << 16); };
+      *reinterpret_cast<uint2*>(coef + h264::COEF_CHROMA_DC + comp * 4) = make_uint2(p2(cl[0], cl[1]), p2(cl[2], cl[3]));
+    }
+    // this block's row of the 2x2 Hadamard (signs by cb: no dynamically indexed array)
+    const int c0 = cl[0], c1 = cl[1], c2 = cl[2], c3 = cl[3];
+    const int fcb = cb == 0 ? c0 + c1 + c2 + c3 : (cb == 1 ? c0 - c1 + c2 - c3 : (cb == 2 ? c0 + c1 - c2 - c3 : c0 - c1 - c2 + c3));
+    const int ls = 16 * dvc[0];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) res[r] = (keep_ac && r > 0) ? (lv[r] * dvc[h264::kPosClass[r]]) << (qpc / 6) : 0;
+    res[0] = ((fcb * ls) << (qpc / 6)) >> 5;
+    const bool any = any_ac || c0 || c1 || c2 || c3;
+    any_c = any;
+    if (any) h264::inverse_core4x4(res);
+    uint8_t* recc = (comp == 0 ? a.rec_u : a.rec_v) + rcur * g.csize() + static_cast<size_t>(my * 8 + cby) * cw + mx * 8 + cbx;
+#pragma unroll
+    for (int y = 0; y < 4; ++y) {
+      int v4[4];
+#pragma unroll
+      for (int x = 0; x < 4; ++x)
+        v4[x] = h264::clip1(static_cast<int>(__builtin_amdgcn_ubfe(prw[y], 8 * x, 8)) + (any ? res[y * 4 + x] : 0));
+      *reinterpret_cast<uint32_t*>(recc + static_cast<size_t>(y) * cw) = pack4_u8(v4);
+    }
+  }
+  if (a.qp_flags) {
+    // encode_inter_mb wrote the MB's byte from luma; an MB coded here with a chroma level has 1
+    const uint64_t chroma_any = __ballot(any_c);
+    if (work && (lane & 7) == 0 && ((chroma_any >> (8 * m)) & 0xFFu) != 0) a.qp_flags[o] = 1;
   }
 }
 
@@ -716,4 +784,5 @@ extern "C" void mivc_launch_encode_inter(int B, int wmb, int hmb, const uint8_t*
   a.bmode = bmode;
   a.t8 = t8;
   hipLaunchKernelGGL(encode_inter_mb, dim3(mb_row_grid(wmb * hmb), B), dim3(64), 0, static_cast<hipStream_t>(stream), a);
+  hipLaunchKernelGGL(encode_inter_chroma, dim3(chroma_wave_grid(wmb * hmb), B), dim3(64), 0, static_cast<hipStream_t>(stream), a);
 }

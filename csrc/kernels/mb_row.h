@@ -14,6 +14,10 @@ constexpr int kMbsPerWave = 4;
 // grid.x of a (units, slots) launch with 64 threads per workgroup
 inline int mb_row_grid(int nmb) { return (nmb + kMbsPerWave - 1) / kMbsPerWave; }
 
+// 4:2:0 chroma of an MB is eight 4x4 blocks, a lane each: eight MBs per wave (encode_inter_chroma)
+constexpr int kMbsPerChromaWave = 8;
+inline int chroma_wave_grid(int nmb) { return (nmb + kMbsPerChromaWave - 1) / kMbsPerChromaWave; }
+
 struct MbRow {
   int slot, mb;  // mb: raster index in the slot's picture
   int lane;      // 0..15: this lane's 4x4 block of the MB, raster order

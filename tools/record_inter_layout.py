@@ -2,8 +2,10 @@
 """Record the golden bitstream hashes of tests/test_gpu_inter_layout.py (suite ``inter``),
 tests/test_gpu_decide_layout.py (suite ``decide``), tests/test_gpu_gate_layout.py (suite ``gate``)
 and tests/test_gpu_intra_free.py (suite ``intra``: planted intra MBs of P / B pictures, with the
-counts of free and chained ones per case) and tests/test_gpu_source_pass.py (suite ``source``: the
-clips of the padding / AQ and mb_qp_delta flag tests through ``encode``).
+counts of free and chained ones per case), tests/test_gpu_source_pass.py (suite ``source``: the
+clips of the padding / AQ and mb_qp_delta flag tests through ``encode``) and
+tests/test_gpu_inter_chroma8.py (suite ``chroma8``: the chroma launch of the inter residual, eight
+MBs per wave; with the record statistics and the mb_qp_delta flag bytes per case).
 
 The tests pin the bytes of small encodes, at shapes where the four-MBs-per-wave lane layout can
 go wrong, to what the *parent* build of the kernels emits.  So this recorder never runs on the
@@ -16,6 +18,7 @@ commit, e.g.
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py gate tests/golden/gate_layout_parent.json
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py intra tests/golden/intra_free_parent.json
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py source tests/golden/source_pass_parent.json
+    MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py chroma8 tests/golden/inter_chroma8_parent.json
 
 The file holds, per case, the arguments (size, frames, clip seed / class, parameter overrides)
 and the SHA-256 of every slot's bitstream.  Per case it also prints what the test asserts
@@ -204,6 +207,43 @@ SOURCE_CASES = [
 ] + [
     dict(id="flags-80x48-per-slot-plans", clip="flags", width=80, height=48, slots=2, frames=6, seed=61,
          anchors_at=[[3], [2]], need_flags=True, params=dict(_FLG, trellis=2)),
+]
+
+# The chroma launch of the inter residual (encode_inter_chroma: eight MBs per wave): see
+# tests/test_gpu_inter_chroma8.py, whose clip builder, spy and statistics this suite runs.  Sizes
+# by nmb % 8: 48x32 -> 6 MBs (one partly filled wave), 48x48 -> 9 (one live MB in the second
+# wave), 64x48 -> 12 (four), 80x48 -> 15 (seven; 5 MBs per row), 96x48 -> 18 (two), 112x48 -> 21
+# (7 MBs per row: every wave straddles rows), 176x144 -> 99.  AQ is on everywhere (qp_flags live).
+_C8P = dict(crf=None, bframes=0, aq_strength=1.0)
+_C8B = dict(crf=None, bframes=3, weightb=True, aq_strength=1.0, lookahead=False)
+
+
+def _c8(id_, family, w, h, frames, seed, kind, **params):
+    return dict(id=id_, family=family, width=w, height=h, frames=frames, seed=seed, kind=kind, params=params)
+
+
+CHROMA8_CASES = [
+    _c8("48x32-p-part-t8-trellis2", "p-part", 48, 32, 6, 71, "default", qp=26, t8x8=True, trellis=2, chroma_qp_offset=-4,
+        **_C8P, **_PART),
+    _c8("112x48-p-part-not8-trellis0", "p-part", 112, 48, 6, 72, "zoom", qp=24, t8x8=False, trellis=0, **_C8P, **_PART),
+    _c8("176x144-p-part-t8-trellis2", "p-part", 176, 144, 5, 73, "default", qp=28, t8x8=True, trellis=2,
+        chroma_qp_offset=-6, **_C8P, **_PART),
+    _c8("64x48-p-refs3-weightp-trellis2", "p-refs", 64, 48, 7, 74, "fade", qp=26, t8x8=False, trellis=2, refs=3,
+        weightp=True, chroma_qp_offset=-4, **_C8P),
+    _c8("80x48-p-refs3-weightp-t8-trellis0", "p-refs", 80, 48, 7, 75, "fade", qp=28, t8x8=True, trellis=0, refs=3,
+        weightp=True, chroma_qp_offset=-6, **_C8P),
+    _c8("176x144-p-refs3-weightp-trellis2", "p-refs", 176, 144, 6, 76, "fade", qp=26, t8x8=True, trellis=2, refs=3,
+        weightp=True, ref_gate=0, chroma_qp_offset=-4, **_C8P),
+    _c8("48x48-b-not8-trellis0", "b-weightb", 48, 48, 9, 77, "default", qp=26, t8x8=False, trellis=0, chroma_qp_offset=-4,
+        **_C8B),
+    _c8("80x48-b-t8-trellis2", "b-weightb", 80, 48, 9, 78, "pan-fast", qp=28, t8x8=True, trellis=2, chroma_qp_offset=-6,
+        **_C8B),
+    _c8("112x48-b-t8-trellis2", "b-weightb", 112, 48, 9, 79, "default", qp=24, t8x8=True, trellis=2, **_C8B),
+    _c8("176x144-b-refs3-trellis0", "b-weightb", 176, 144, 9, 80, "zoom", qp=28, t8x8=True, trellis=0, refs=3,
+        chroma_qp_offset=-6, **_C8B),
+    # noise at a low QP (every block has levels), in the families of their picture types
+    _c8("96x48-p-part-noise-lowqp", "p-part", 96, 48, 6, 81, "noise", qp=18, t8x8=True, trellis=2, **_C8P, **_PART),
+    _c8("96x48-b-noise-lowqp", "b-weightb", 96, 48, 9, 82, "noise", qp=16, t8x8=True, trellis=2, **_C8B),
 ]
 
 INTRA_KINDS = (0, 1, 4, 8)
@@ -400,6 +440,36 @@ def record_source(host, path) -> None:
         f.write("\n")
 
 
+def record_chroma8(host, path) -> None:
+    """Suite ``chroma8``: per case the per-slot hashes, the record statistics and the counts of the
+    mb_qp_delta flag bytes.  The clips, the spy and the statistics are the test's own (the test
+    module reads the golden file when imported, so a first recording starts from an empty one)."""
+    if not os.path.exists(path):
+        with open(path, "w") as f:
+            json.dump(dict(slots=SLOTS, cases=[]), f)
+    from tests import test_gpu_inter_chroma8 as T
+
+    rows, fam = [], {}
+    for case in CHROMA8_CASES:
+        case = json.loads(json.dumps(case))  # as the test will read it
+        enc, res, spy = T.encode(case, SLOTS)
+        streams = [bytes(r.bitstream) for r in res]
+        enc.close()
+        stats = T.chroma_stats(host, streams)
+        print(case["id"], [len(s) for s in streams], stats, "flag bytes", spy.counts, flush=True)
+        tot = fam.setdefault(case["family"], {})
+        for k, n in list(stats.items()) + [(f"flag{k}", n) for k, n in spy.counts.items()]:
+            tot[k] = tot.get(k, 0) + n
+        rows.append(dict(case, stats=stats, flag_bytes={str(k): n for k, n in spy.counts.items()},
+                         sha256=[hashlib.sha256(s).hexdigest() for s in streams]))
+    for name, tot in fam.items():
+        vac = [k for k in T._NEED[name] + ("flag0", "flag1", "flag2") if tot[k] == 0]
+        print("family", name, tot, "VACUOUS: " + ",".join(vac) if vac else "", flush=True)
+    with open(path, "w") as f:
+        json.dump(dict(slots=SLOTS, cases=rows), f, indent=1)
+        f.write("\n")
+
+
 def np_isin_any(a, values) -> bool:
     import numpy as np
 
@@ -408,7 +478,7 @@ def np_isin_any(a, values) -> bool:
 
 def main() -> None:
     suite = "inter"
-    if len(sys.argv) == 3 and sys.argv[1] in ("inter", "decide", "gate", "intra", "source"):
+    if len(sys.argv) == 3 and sys.argv[1] in ("inter", "decide", "gate", "intra", "source", "chroma8"):
         suite = sys.argv.pop(1)
     if len(sys.argv) != 2:
         raise SystemExit(__doc__)
@@ -424,6 +494,9 @@ def main() -> None:
         return
     if suite == "source":
         record_source(host, sys.argv[1])
+        return
+    if suite == "chroma8":
+        record_chroma8(host, sys.argv[1])
         return
     if suite == "gate":
         for case in GATE_CASES:
