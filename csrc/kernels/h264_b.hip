@@ -268,9 +268,13 @@ __device__ __forceinline__ void b_decide_main(const BDecideArgs& a, const MbRow&
     s_pair[wrow][3][lane] = s3 + dpp<kDppQuadXor1>(s3);
   }
   const int w10 = w1of(0);
+  {
+    uint32_t p1[4];
+    mc4x4(G0, H0, W, H, X, Y, m0x, m0y, pb);
+    mc4x4(G1, H1, W, H, X, Y, m1x, m1y, p1);
 #pragma unroll
-  for (int y = 0; y < 4; ++y)
-    pb[y] = wavg4b(mc4(G0, H0, W, H, X, Y + y, m0x, m0y), mc4(G1, H1, W, H, X, Y + y, m1x, m1y), w10);
+    for (int y = 0; y < 4; ++y) pb[y] = wavg4b(pb[y], p1[y], w10);
+  }
   {
     const int s1 = satd4x4_u8(src, pb);
     s_pair[wrow][1][lane] = s1 + dpp<kDppQuadXor1>(s1);
@@ -517,10 +521,12 @@ __global__ __launch_bounds__(64) void b_decide(BDecideArgs a) {
     const uint8_t *GD = dr ? a.ref0k[dr] + (a.rt ? sd : slot) * g.ysize() : G0,
                   *HD = dr ? a.hp0k[dr] + (a.rt ? sd : slot) * hps : H0;
     const int w1 = w1of(dr);
-    uint32_t pd[4];
+    uint32_t pd[4], p1[4];
+    mc4x4(GD, HD, W, H, X, Y, dvx0, dvy0, pd);
+    mc4x4(G1, H1, W, H, X, Y, dvx1, dvy1, p1);
 #pragma unroll
     for (int y = 0; y < 4; ++y) {
-      pd[y] = wavg4b(mc4(GD, HD, W, H, X, Y + y, dvx0, dvy0), mc4(G1, H1, W, H, X, Y + y, dvx1, dvy1), w1);
+      pd[y] = wavg4b(pd[y], p1[y], w1);
       *reinterpret_cast<uint32_t*>(pout + 16 * y) = pd[y];
     }
     const int sat = row_satd(src, pd);

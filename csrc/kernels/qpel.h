@@ -88,5 +88,51 @@ __device__ __forceinline__ uint32_t mc4(const uint8_t* G, const uint8_t* hp, int
   return avg4b(A, Bv);
 }
 
+// 8 bytes at a 4-byte aligned address as one access (global_load_dwordx2)
+struct __attribute__((packed, aligned(4))) QpelPair {
+  uint32_t lo, hi;
+};
+
+// plane4 of the four rows v .. v+3, the work that does not depend on the row done once: one
+// inside test for the block (the rows need no clamp, and the aligned 8 bytes lie in the plane:
+// plane4's condition for every row -- its u + 3 <= hi follows from the 8 bytes fitting), then
+// four 8-byte loads a pitch apart.  Any other block goes through plane4 row by row.
+__device__ __forceinline__ void plane4x4(const uint8_t* G, const uint8_t* hp, int W, int H, int pl, int u, int v,
+                                         uint32_t (&out)[4]) {
+  const int PW = W + 2 * kHpMargin, PH = H + 2 * kHpMargin;
+  const int m = pl == 0 ? 0 : kHpMargin, pitch = pl == 0 ? W : PW;
+  const int x = u + m, a = x & ~3;
+  if (u >= -m && a + 8 <= pitch && v >= -m && v + 3 <= H + m - 1) {
+    const uint8_t* p = (pl == 0 ? G : hp + static_cast<size_t>(pl - 1) * PW * PH) +
+                       static_cast<size_t>(v + m) * pitch + a;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const QpelPair w = *reinterpret_cast<const QpelPair*>(p + static_cast<size_t>(k) * pitch);
+      out[k] = __builtin_amdgcn_alignbyte(w.hi, w.lo, x & 3);
+    }
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) out[k] = plane4(G, hp, W, H, pl, u, v + k);
+}
+
+// the 4x4 block at (x, y) displaced by the quarter-sample vector, as four packed rows: equal
+// to mc4 of rows y .. y+3 bit for bit.  The phase, the taps and the addresses are worked out
+// once for the block; a phase whose two taps are the same sample (integer and pure half
+// positions) fetches it once, avg4b(A, A) being A.
+__device__ __forceinline__ void mc4x4(const uint8_t* G, const uint8_t* hp, int W, int H, int x, int y, int mvx,
+                                      int mvy, uint32_t (&out)[4]) {
+  const int q = (mvy & 3) * 4 + (mvx & 3);
+  const int xi = x + (mvx >> 2), yi = y + (mvy >> 2);
+  const int p0 = kQTap[q][0][0], u0 = kQTap[q][0][1], v0 = kQTap[q][0][2];
+  const int p1 = kQTap[q][1][0], u1 = kQTap[q][1][1], v1 = kQTap[q][1][2];
+  plane4x4(G, hp, W, H, p0, xi + u0, yi + v0, out);
+  if (p0 == p1 && u0 == u1 && v0 == v1) return;
+  uint32_t b[4];
+  plane4x4(G, hp, W, H, p1, xi + u1, yi + v1, b);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) out[k] = avg4b(out[k], b[k]);
+}
+
 }  // namespace gpu
 }  // namespace mivc

@@ -5,7 +5,9 @@ and tests/test_gpu_intra_free.py (suite ``intra``: planted intra MBs of P / B pi
 counts of free and chained ones per case), tests/test_gpu_source_pass.py (suite ``source``: the
 clips of the padding / AQ and mb_qp_delta flag tests through ``encode``) and
 tests/test_gpu_inter_chroma8.py (suite ``chroma8``: the chroma launch of the inter residual, eight
-MBs per wave; with the record statistics and the mb_qp_delta flag bytes per case).
+MBs per wave; with the record statistics and the mb_qp_delta flag bytes per case) and the
+end-to-end cases of tests/test_gpu_b_block_fetch.py (suite ``bfetch``: the B decision's pre-pass
+and main pass; with the gate's counts and the direct MBs / quadrants of the decoded records).
 
 The tests pin the bytes of small encodes, at shapes where the four-MBs-per-wave lane layout can
 go wrong, to what the *parent* build of the kernels emits.  So this recorder never runs on the
@@ -19,6 +21,7 @@ commit, e.g.
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py intra tests/golden/intra_free_parent.json
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py source tests/golden/source_pass_parent.json
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py chroma8 tests/golden/inter_chroma8_parent.json
+    MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py bfetch tests/golden/b_block_fetch_parent.json
 
 The file holds, per case, the arguments (size, frames, clip seed / class, parameter overrides)
 and the SHA-256 of every slot's bitstream.  Per case it also prints what the test asserts
@@ -246,6 +249,32 @@ CHROMA8_CASES = [
     _c8("96x48-b-noise-lowqp", "b-weightb", 96, 48, 9, 82, "noise", qp=16, t8x8=True, trellis=2, **_C8B),
 ]
 
+# The B decision (h264_b.hip: pre-pass, gated searches, main pass over the searched MBs): see
+# tests/test_gpu_b_block_fetch.py, whose clip builder and statistics this suite runs.  need: the
+# counts the case is there for (the wavefront decides direct against explicit itself: searched
+# MBs get no direct quadrant from b_decide).
+_BF = dict(crf=None, bframes=3, lookahead=False)
+_BF_ALL = ["b_gated", "b_searched", "direct"]
+
+
+def _bf(id_, w, h, frames, seed, kind, need, **params):
+    return dict(id=id_, width=w, height=h, frames=frames, seed=seed, kind=kind, need=need, params=dict(_BF, **params))
+
+
+BFETCH_CASES = [
+    _bf("48x48-temporal-weightb", 48, 48, 9, 91, "default", _BF_ALL, qp=26, weightb=True, refs=1, partitions=False),
+    _bf("80x48-temporal-weightb-aq-bgate-600", 80, 48, 9, 92, "default", _BF_ALL, qp=24, weightb=True, refs=1,
+        aq_strength=1.0, b_gate=-600, partitions=False),
+    _bf("176x144-refs2-pyramid", 176, 144, 9, 93, "default", _BF_ALL, qp=26, weightb=True, refs=2, pyramid=True),
+    _bf("80x48-bpartitions", 80, 48, 9, 94, "default", _BF_ALL + ["b8x8_direct"], qp=24, weightb=True, refs=1,
+        partitions=True, bpartitions=True, part_overhead=0, part_min_satd=0),
+    _bf("176x144-bpartitions-zoom", 176, 144, 7, 95, "zoom", _BF_ALL + ["b8x8_direct"], qp=26, weightb=False, refs=1,
+        partitions=True, bpartitions=True),
+    _bf("80x48-spatial-fast", 80, 48, 9, 96, "default", _BF_ALL, qp=26, weightb=True, refs=1, direct="spatial"),
+    _bf("176x144-spatial-wavefront-gate", 176, 144, 7, 97, "default", _BF_ALL, qp=26, weightb=True, refs=1,
+        direct="spatial", spatial_wavefront=True, spatial_gate=True),
+]
+
 INTRA_KINDS = (0, 1, 4, 8)
 SPLIT_KINDS = (5, 6, 7, 10, 11, 12)
 
@@ -470,6 +499,30 @@ def record_chroma8(host, path) -> None:
         f.write("\n")
 
 
+def record_bfetch(host, path) -> None:
+    """Suite ``bfetch``: per case the per-slot hashes, the gate's counts and the direct MBs /
+    quadrants of the decoded records.  The clips and the statistics are the test's own (the test
+    module reads the golden file when imported, so a first recording starts from an empty one)."""
+    if not os.path.exists(path):
+        with open(path, "w") as f:
+            json.dump(dict(slots=SLOTS, cases=[]), f)
+    from tests import test_gpu_b_block_fetch as T
+
+    rows = []
+    for case in BFETCH_CASES:
+        case = json.loads(json.dumps(case))  # as the test will read it
+        enc, res, counts = T.encode(case, SLOTS)
+        streams = [bytes(r.bitstream) for r in res]
+        enc.close()
+        counts.update(T.b_stats(host, streams))
+        vac = [k for k in case["need"] if counts[k] == 0]
+        print(case["id"], [len(s) for s in streams], counts, "VACUOUS: " + ",".join(vac) if vac else "", flush=True)
+        rows.append(dict(case, counts=counts, sha256=[hashlib.sha256(s).hexdigest() for s in streams]))
+    with open(path, "w") as f:
+        json.dump(dict(slots=SLOTS, cases=rows), f, indent=1)
+        f.write("\n")
+
+
 def np_isin_any(a, values) -> bool:
     import numpy as np
 
@@ -478,7 +531,7 @@ def np_isin_any(a, values) -> bool:
 
 def main() -> None:
     suite = "inter"
-    if len(sys.argv) == 3 and sys.argv[1] in ("inter", "decide", "gate", "intra", "source", "chroma8"):
+    if len(sys.argv) == 3 and sys.argv[1] in ("inter", "decide", "gate", "intra", "source", "chroma8", "bfetch"):
         suite = sys.argv.pop(1)
     if len(sys.argv) != 2:
         raise SystemExit(__doc__)
@@ -497,6 +550,9 @@ def main() -> None:
         return
     if suite == "chroma8":
         record_chroma8(host, sys.argv[1])
+        return
+    if suite == "bfetch":
+        record_bfetch(host, sys.argv[1])
         return
     if suite == "gate":
         for case in GATE_CASES:
