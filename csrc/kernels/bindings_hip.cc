@@ -774,6 +774,11 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("slot_qp"), py::arg("out"), py::arg("out_off"), py::arg("stream"), py::arg("nz") = 0);
   m.def("sse", [](int B, int W, int H, int w, int h, uintptr_t sy, uintptr_t su, uintptr_t sv, uintptr_t ry,
                   uintptr_t ru, uintptr_t rv, uintptr_t sse, uintptr_t ssim, uintptr_t stream, uintptr_t route, int nbuf) {
+    // the kernels step through rows of the coded size in 16-byte chunks and halve both sizes for chroma
+    if (B <= 0 || W <= 0 || H <= 0 || W % 16 || H % 2) throw std::invalid_argument("sse: coded width must be a multiple of 16, height even");
+    if (w < 2 || h < 2 || w > W || h > H || w % 2 || h % 2)
+      throw std::invalid_argument("sse: the display window must be even and lie inside the coded size");
+    if (route && nbuf < 1) throw std::invalid_argument("sse: a routed launch needs the pool size");
     mivc_launch_sse(B, W, H, w, h, P<uint8_t>(sy), P<uint8_t>(su), P<uint8_t>(sv), P<uint8_t>(ry), P<uint8_t>(ru),
                     P<uint8_t>(rv), P<unsigned long long>(sse), P<float>(ssim), S(stream), P<void>(route), nbuf);
   }, py::arg("B"), py::arg("W"), py::arg("H"), py::arg("w"), py::arg("h"), py::arg("sy"), py::arg("su"), py::arg("sv"),

@@ -8,14 +8,25 @@ namespace gpu {
 
 // sse: [B, 3] uint64 (Y, U, V).  Grid (blocks_per_slot, B); each block strides over
 // rows, each thread over 16-byte column chunks; one atomic per block and plane.
-__device__ __forceinline__ unsigned sq_diff16(uint4 a, uint4 b, int valid) {
-  const uint8_t* pa = reinterpret_cast<const uint8_t*>(&a);
-  const uint8_t* pb = reinterpret_cast<const uint8_t*>(&b);
+// `valid` bytes of the chunk belong to the row: a whole chunk is one 16-byte load per plane,
+// the last chunk of a row narrower than that is read byte by byte (a whole load would run
+// past the row, and on the last row of the last plane past the tensor)
+__device__ __forceinline__ unsigned sq_diff16(const uint8_t* a, const uint8_t* b, int valid) {
   unsigned s = 0;
+  if (valid >= 16) {
+    const uint4 va = *reinterpret_cast<const uint4*>(a), vb = *reinterpret_cast<const uint4*>(b);
+    const uint8_t* pa = reinterpret_cast<const uint8_t*>(&va);
+    const uint8_t* pb = reinterpret_cast<const uint8_t*>(&vb);
 #pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    int d = static_cast<int>(pa[k]) - pb[k];
-    s += k < valid ? static_cast<unsigned>(d * d) : 0u;
+    for (int k = 0; k < 16; ++k) {
+      int d = static_cast<int>(pa[k]) - pb[k];
+      s += static_cast<unsigned>(d * d);
+    }
+  } else {
+    for (int k = 0; k < valid; ++k) {
+      int d = static_cast<int>(a[k]) - b[k];
+      s += static_cast<unsigned>(d * d);
+    }
   }
   return s;
 }
@@ -35,13 +46,13 @@ __global__ void sse_planes(const uint8_t* sy, const uint8_t* su, const uint8_t* 
   for (int i = tid; i < chunks_y * h; i += nth) {
     int r = i / chunks_y, c = (i % chunks_y) * 16;
     size_t off = yo + static_cast<size_t>(r) * W + c;
-    acc[0] += sq_diff16(*reinterpret_cast<const uint4*>(sy + off), *reinterpret_cast<const uint4*>(ry + off - yo + ryo), w - c);
+    acc[0] += sq_diff16(sy + off, ry + off - yo + ryo, w - c);
   }
   for (int i = tid; i < chunks_c * (h / 2); i += nth) {
     int r = i / chunks_c, c = (i % chunks_c) * 16;
     size_t off = co + static_cast<size_t>(r) * (W / 2) + c;
-    acc[1] += sq_diff16(*reinterpret_cast<const uint4*>(su + off), *reinterpret_cast<const uint4*>(ru + off - co + rco), w / 2 - c);
-    acc[2] += sq_diff16(*reinterpret_cast<const uint4*>(sv + off), *reinterpret_cast<const uint4*>(rv + off - co + rco), w / 2 - c);
+    acc[1] += sq_diff16(su + off, ru + off - co + rco, w / 2 - c);
+    acc[2] += sq_diff16(sv + off, rv + off - co + rco, w / 2 - c);
   }
   __shared__ unsigned long long red[3][4];
   for (int p = 0; p < 3; ++p) {
