@@ -204,6 +204,68 @@ MIVC_HD int mc_luma_sample(const P& ref, int xi, int yi, int xf, int yf) {
   return (b + h + 1) >> 1;
 }
 
+// ---------------------------------------------------------------- samples of more than 8 bits
+// Overloads for BitDepth 9..14 (High 10 and up): maxv = (1 << BitDepth) - 1 bounds the clips
+// and half = 1 << (BitDepth - 1) is the DC prediction without neighbours.  The 8-bit
+// functions above are maxv = 255, half = 128.
+MIVC_HD int clip1(int v, int maxv) { return v < 0 ? 0 : (v > maxv ? maxv : v); }
+
+MIVC_HD int i4_pred_sample(int mode, int av, const int* e, int x, int y, int half) {
+  if (mode == 2 && !(av & (AV_TOP | AV_LEFT))) return half;
+  return i4_pred_sample(mode, av, e, x, y);
+}
+template <class T>
+MIVC_HD int i16_dc(const T* top, const T* left, int av, int half) {
+  return (av & (AV_TOP | AV_LEFT)) ? i16_dc(top, left, av) : half;
+}
+template <class T>
+MIVC_HD int chroma_dc(const T* top, const T* left, int av, int bx, int by, int half) {
+  return (av & (AV_TOP | AV_LEFT)) ? chroma_dc(top, left, av, bx, by) : half;
+}
+
+template <class P>
+MIVC_HD int mc_luma_sample(const P& ref, int xi, int yi, int xf, int yf, int maxv) {
+  auto b1 = [&](int x, int y) {
+    return tap6(ref(x - 2, y), ref(x - 1, y), ref(x, y), ref(x + 1, y), ref(x + 2, y), ref(x + 3, y));
+  };
+  auto h1 = [&](int x, int y) {
+    return tap6(ref(x, y - 2), ref(x, y - 1), ref(x, y), ref(x, y + 1), ref(x, y + 2), ref(x, y + 3));
+  };
+  auto B = [&](int x, int y) { return clip1((b1(x, y) + 16) >> 5, maxv); };
+  auto Hh = [&](int x, int y) { return clip1((h1(x, y) + 16) >> 5, maxv); };
+  auto J = [&](int x, int y) {
+    int j1 = tap6(h1(x - 2, y), h1(x - 1, y), h1(x, y), h1(x + 1, y), h1(x + 2, y), h1(x + 3, y));
+    return clip1((j1 + 512) >> 10, maxv);
+  };
+  if (xf == 0 && yf == 0) return ref(xi, yi);
+  if (yf == 0) {
+    int b = B(xi, yi);
+    if (xf == 1) return (ref(xi, yi) + b + 1) >> 1;
+    if (xf == 2) return b;
+    return (ref(xi + 1, yi) + b + 1) >> 1;
+  }
+  if (xf == 0) {
+    int h = Hh(xi, yi);
+    if (yf == 1) return (ref(xi, yi) + h + 1) >> 1;
+    if (yf == 2) return h;
+    return (ref(xi, yi + 1) + h + 1) >> 1;
+  }
+  if (xf == 2 && yf == 2) return J(xi, yi);
+  if (xf == 2) {  // f (yf=1) or q (yf=3)
+    int j = J(xi, yi);
+    int b = yf == 1 ? B(xi, yi) : B(xi, yi + 1);
+    return (b + j + 1) >> 1;
+  }
+  if (yf == 2) {  // i (xf=1) or k (xf=3)
+    int j = J(xi, yi);
+    int h = xf == 1 ? Hh(xi, yi) : Hh(xi + 1, yi);
+    return (h + j + 1) >> 1;
+  }
+  int b = yf == 1 ? B(xi, yi) : B(xi, yi + 1);
+  int h = xf == 1 ? Hh(xi, yi) : Hh(xi + 1, yi);
+  return (b + h + 1) >> 1;
+}
+
 template <class P>
 MIVC_HD int mc_chroma_sample(const P& ref, int xi, int yi, int xf, int yf) {
   return ((8 - xf) * (8 - yf) * ref(xi, yi) + xf * (8 - yf) * ref(xi + 1, yi) + (8 - xf) * yf * ref(xi, yi + 1) +

@@ -156,6 +156,17 @@ py::array_t<int32_t> segment_meta(const ParsedSegment& seg) {
   return meta;
 }
 
+// bit_depth (of the first picture) and gpu_ok16 [P]: gpu_ok but for the bit depth (9- and
+// 10-bit pictures the 16-bit reconstruction kernels take)
+void segment_depth(const ParsedSegment& seg, py::dict& d) {
+  const py::ssize_t P = static_cast<py::ssize_t>(seg.pics.size());
+  d["bit_depth"] = seg.pics[0].bit_depth;
+  py::array_t<uint8_t> ok16(P);
+  for (py::ssize_t i = 0; i < P; ++i)
+    ok16.mutable_data()[i] = seg.pics[i].gpu_ok16 && seg.pics[i].bit_depth == seg.pics[0].bit_depth ? 1 : 0;
+  d["gpu_ok16"] = ok16;
+}
+
 // the small tables of a parsed segment for the GPU decoder's planning (no per-MB records)
 py::dict segment_info(const ParsedSegment& seg) {
   py::dict d;
@@ -180,6 +191,7 @@ py::dict segment_info(const ParsedSegment& seg) {
     return d;
   }
   d["meta"] = segment_meta(seg);
+  segment_depth(seg, d);
   py::array_t<int32_t> lists({P, static_cast<py::ssize_t>(2), static_cast<py::ssize_t>(32)});
   for (py::ssize_t i = 0; i < P; ++i) std::memcpy(lists.mutable_data() + i * 64, seg.pics[i].list_ids.data(), 64 * 4);
   d["lists"] = lists;
@@ -258,6 +270,7 @@ py::dict segment_to_dict(ParsedSegment& seg) {
   d["coef"] = vec_array<int16_t>(coef, {static_cast<py::ssize_t>(po[P] * 16)});
   d["pic_off"] = pic_off;
   d["meta"] = meta;
+  segment_depth(seg, d);
   d["sub"] = vec_array<int16_t>(subs, {static_cast<py::ssize_t>(so[P] * kSubEntry)});
   d["sub_off"] = sub_off;
   d["bs"] = vec_array<uint8_t>(bss, {P, nmb, 16});

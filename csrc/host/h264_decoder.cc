@@ -83,6 +83,7 @@ struct Pic {
   std::vector<uint32_t> rec_mask, rec_off;
   std::vector<int16_t> rec_sub;  // parse-only: kSubEntry int16 per MB with sub-8x8 motion
   bool gpu_ok = true;
+  bool gpu_ok16 = true;  // as gpu_ok, but 9- and 10-bit samples are fine (the 16-bit kernels)
   int nslices = 0;
   int slice_qp = 0;
   std::vector<int32_t> list_ids;  // parse-only: reference lists of the (single) slice
@@ -148,6 +149,7 @@ struct Pic {
     long_idx = -1;
     mmco5 = false;
     gpu_ok = true;
+    gpu_ok16 = true;
     nslices = 0;
     slice_qp = 0;
     list_ids.clear();
@@ -554,7 +556,7 @@ struct Decoder::Impl {
       // 1 / 2 per edge) and the chroma QP offset; MbHeader::pad0 carries the slice for the
       // intra kernel's neighbour availability
       const SliceParams* f = nullptr;
-      bool ok = cur->gpu_ok && cur->nslices <= 255 && !cur->mmco5;
+      bool ok = cur->nslices <= 255 && !cur->mmco5;
       for (const SliceParams& sp2 : slices) {
         ok = ok && sp2.cb_off == sp2.cr_off && sp2.cb_off == slices[0].cb_off;
         if (sp2.disable_idc == 1) continue;
@@ -565,7 +567,9 @@ struct Decoder::Impl {
       d.beta_off = f ? f->beta_off : 0;
       d.chroma_qp_offset = slices.empty() ? 0 : slices[0].cb_off;
       d.deblock = f != nullptr;
-      d.gpu_ok = ok;
+      d.gpu_ok = ok && cur->gpu_ok;
+      d.gpu_ok16 = ok && cur->gpu_ok16;
+      d.bit_depth = bdY;
       d.poc = cur->poc;
       d.sub = std::move(cur->rec_sub);
       d.list_ids = cur->list_ids.empty() ? std::vector<int32_t>(64, -1) : cur->list_ids;
@@ -731,7 +735,8 @@ struct Decoder::Impl {
     qpbdC = 6 * (bdC - 8);
     cur = new_pic();
     cur->init(sp->width_mbs, sp->height_mbs, !parse_only);
-    if (bdY != 8 || bdC != 8) cur->gpu_ok = false;  // the GPU reconstruction kernels are 8-bit
+    if (bdY != 8 || bdC != 8) cur->gpu_ok = false;  // the default GPU reconstruction kernels are 8-bit
+    if (bdY != bdC || bdY > 10) cur->gpu_ok16 = false;  // the 16-bit ones take 9 and 10 bits
     if (parse_only) cur->init_records();
     cur->slice_qp = h.qp;
     pic_ref_id = -1;
@@ -2542,9 +2547,19 @@ struct Decoder::Impl {
       mask |= 1u << bit;
       size_t b = cur->rec_coef.size();
       cur->rec_coef.resize(b + 16, 0);
-      for (int i = 0; i < n; ++i) cur->rec_coef[b + i] = static_cast<int16_t>(v[i]);
+      // the pool is int16: a level outside it (legal in High 10 at very low QP) cannot ride
+      // there, so such a picture is not one for the 16-bit kernels
+      bool wide = false;
+      for (int i = 0; i < n; ++i) {
+        cur->rec_coef[b + i] = static_cast<int16_t>(v[i]);
+        wide |= cur->rec_coef[b + i] != v[i];
+      }
       if (v2)
-        for (int i = 0; i < n; ++i) cur->rec_coef[b + n + i] = static_cast<int16_t>(v2[i]);
+        for (int i = 0; i < n; ++i) {
+          cur->rec_coef[b + n + i] = static_cast<int16_t>(v2[i]);
+          wide |= cur->rec_coef[b + n + i] != v2[i];
+        }
+      if (wide) cur->gpu_ok16 = false;
     };
     // only the blocks the coded_block_pattern codes are read (decode_mb leaves the others
     // uncleared in parse-only mode)
@@ -2747,14 +2762,14 @@ struct Decoder::Impl {
         }
     } else if (sh.slice_type == SLICE_B && pp->weighted_bipred_idc == 2) {
       w[0] = 2;
-      if (sh.num_ref_idx_l0_active > 8 || sh.num_ref_idx_l1_active > 8) cur->gpu_ok = false;
+      if (sh.num_ref_idx_l0_active > 8 || sh.num_ref_idx_l1_active > 8) cur->gpu_ok = cur->gpu_ok16 = false;
       for (int i = 0; i < 8 && i < sh.num_ref_idx_l0_active; ++i)
         for (int j = 0; j < 8 && j < sh.num_ref_idx_l1_active; ++j) {
           w[kWpImp + (i * 8 + j) * 2] = static_cast<int16_t>(implicit_w[i][j][0]);
           w[kWpImp + (i * 8 + j) * 2 + 1] = static_cast<int16_t>(implicit_w[i][j][1]);
         }
     }
-    if (cur->nslices > 1 && (prev_ids != cur->list_ids || prev_wp != cur->wp)) cur->gpu_ok = false;
+    if (cur->nslices > 1 && (prev_ids != cur->list_ids || prev_wp != cur->wp)) cur->gpu_ok = cur->gpu_ok16 = false;
   }
 
   // parse-only: boundary strength of every filtered edge segment (deblock.hip reads these

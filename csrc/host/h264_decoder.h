@@ -59,6 +59,8 @@ struct DecodedPicture {
   int slice_qp = 0, alpha_off = 0, beta_off = 0, chroma_qp_offset = 0, deblock = 1;
   bool gpu_ok = true;                 // false: a feature the GPU path does not cover (I_PCM,
                                       // Intra8x8, several slices, constrained intra, mmco5 ...)
+  bool gpu_ok16 = true;               // as gpu_ok, but for the bit depth: BitDepthY == BitDepthC <= 10
+                                      // and every level fits the int16 pool (the 16-bit kernels)
   // parse-only motion / filter side info for GPU reconstruction of P and B pictures
   // (per-8x8 quadrant motion is in hdr; MBs with smaller partitions carry MBF_SUB4 and a
   // kSubEntry side-pool entry, csrc/common/h264_mb.h)

@@ -113,6 +113,14 @@ void mivc_launch_decode_picture_dpb(int B, int wmb, int hmb, int dpb_n, uint8_t*
 void mivc_launch_deblock_dpb(int B, int wmb, int hmb, int dpb_n, uint8_t* dpb_y, uint8_t* dpb_u, uint8_t* dpb_v,
                              const int16_t* cur_idx, const void* hdr, const uint8_t* nz, const uint8_t* bs,
                              int chroma_qp_offset, int alpha_off, int beta_off, int* err, void* stream);
+void mivc_launch_decode_picture_dpb16(int B, int wmb, int hmb, int dpb_n, uint16_t* dpb_y, uint16_t* dpb_u,
+                                      uint16_t* dpb_v, const int16_t* cur_idx, const int16_t* reftab, const int16_t* wp,
+                                      const int16_t* sub, const void* hdr, const uint32_t* mask, const uint32_t* off,
+                                      const int16_t* coef, const int8_t* run, int any_inter, int chroma_qp_offset, int bd,
+                                      uint8_t* nz, int* err, void* stream);
+void mivc_launch_deblock_dpb16(int B, int wmb, int hmb, int dpb_n, uint16_t* dpb_y, uint16_t* dpb_u, uint16_t* dpb_v,
+                               const int16_t* cur_idx, const void* hdr, const uint8_t* bs, int chroma_qp_offset,
+                               int alpha_off, int beta_off, int bd, int* err, void* stream);
 int mivc_launch_scale(const void* in, int w, int h, long long in_stride, long long in_pitch, void* out, int ow, int oh,
                       int W, int H, long long out_stride, long long out_pitch, int nframes, const int* fx,
                       const int16_t* cx, int tx, const int* fy, const int16_t* cy, int ty, int tile_w, int tile_h,
@@ -494,6 +502,29 @@ PYBIND11_MODULE(_hip, m) {
     mivc_launch_deblock_dpb(B, wmb, hmb, dpb_n, P<uint8_t>(y), P<uint8_t>(u), P<uint8_t>(v), P<int16_t>(cur_idx),
                             P<void>(hdr), P<uint8_t>(nz), P<uint8_t>(bs), cqo, alpha_off, beta_off, P<int>(err),
                             S(stream));
+  });
+  // High 10: the same two steps on planes of 16-bit samples (bit_depth 9 or 10)
+  m.def("decode_picture_dpb16", [](int B, int wmb, int hmb, int dpb_n, uintptr_t y, uintptr_t u, uintptr_t v,
+                                   uintptr_t cur_idx, uintptr_t reftab, uintptr_t wp, uintptr_t sub,
+                                   uintptr_t hdr, uintptr_t mask, uintptr_t off, uintptr_t coef, uintptr_t run,
+                                   int any_inter, int cqo, int bit_depth, uintptr_t nz, uintptr_t err,
+                                   uintptr_t stream) {
+    if (dpb_n < 1 || dpb_n > 32767) throw std::invalid_argument("decode_picture_dpb16: dpb_n must be 1..32767");
+    if (bit_depth != 9 && bit_depth != 10) throw std::invalid_argument("decode_picture_dpb16: bit_depth must be 9 or 10");
+    mivc_launch_decode_picture_dpb16(B, wmb, hmb, dpb_n, P<uint16_t>(y), P<uint16_t>(u), P<uint16_t>(v),
+                                     P<int16_t>(cur_idx), P<int16_t>(reftab), P<int16_t>(wp), P<int16_t>(sub),
+                                     P<void>(hdr), P<uint32_t>(mask), P<uint32_t>(off), P<int16_t>(coef),
+                                     P<int8_t>(run), any_inter, cqo, bit_depth, P<uint8_t>(nz), P<int>(err), S(stream));
+  });
+  m.def("deblock_dpb16", [](int B, int wmb, int hmb, int dpb_n, uintptr_t y, uintptr_t u, uintptr_t v,
+                            uintptr_t cur_idx, uintptr_t hdr, uintptr_t bs, int cqo, int alpha_off, int beta_off,
+                            int bit_depth, uintptr_t err, uintptr_t stream) {
+    if (dpb_n < 1 || dpb_n > 32767) throw std::invalid_argument("deblock_dpb16: dpb_n must be 1..32767");
+    if (bit_depth != 9 && bit_depth != 10) throw std::invalid_argument("deblock_dpb16: bit_depth must be 9 or 10");
+    if (hmb < 1 || hmb > 272) throw std::invalid_argument("deblock_dpb16: at most 272 MB rows");
+    mivc_launch_deblock_dpb16(B, wmb, hmb, dpb_n, P<uint16_t>(y), P<uint16_t>(u), P<uint16_t>(v), P<int16_t>(cur_idx),
+                              P<void>(hdr), P<uint8_t>(bs), cqo, alpha_off, beta_off, bit_depth, P<int>(err),
+                              S(stream));
   });
   m.def("scale", [](uintptr_t in, int w, int h, long long in_stride, long long in_pitch, uintptr_t out, int ow, int oh,
                     int W, int H, long long out_stride, long long out_pitch, int n, uintptr_t fx, uintptr_t cx, int tx,

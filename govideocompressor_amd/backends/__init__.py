@@ -30,11 +30,16 @@ class _Adapter:
 
 
 def get_backend(name: str = "auto", **kw) -> _Adapter:
+    """``h264_high_depth`` ("cpu" / "gpu") is an option of the GPU backend's decoder; the other
+    backends decode on the CPU anyway and do not see it."""
+    high_depth = kw.pop("h264_high_depth", None)
     if name == "auto":
         import torch
         name = "gpu" if torch.cuda.is_available() else "cpu"
     if name == "gpu":
         from .gpu import GpuBackend
+        if high_depth is not None:
+            kw["h264_high_depth"] = high_depth
         return _Adapter(GpuBackend(**kw))
     if name == "cpu":
         from .cpu_ref import CpuBackend

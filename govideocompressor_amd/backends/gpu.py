@@ -27,8 +27,14 @@ from .common import (BackendError, PieceJob, PieceResult, Timer, idr_id, load_cl
 class GpuBackend:
     name = "gpu"
 
-    def __init__(self, device: str = "cuda", entropy: str = "gpu", max_slots: int = 256):
+    def __init__(self, device: str = "cuda", entropy: str = "gpu", max_slots: int = 256,
+                 h264_high_depth: str = "cpu"):
+        """``h264_high_depth``: where 9- / 10-bit H.264 input reconstructs -- ``"cpu"`` (the CPU
+        decoder, the default) or ``"gpu"`` (``GpuH264Decoder(high_depth="gpu")``)."""
         import torch
+        if h264_high_depth not in ("cpu", "gpu"):
+            raise BackendError("h264_high_depth must be 'cpu' or 'gpu'")
+        self.h264_high_depth = h264_high_depth
         if not torch.cuda.is_available():
             raise BackendError("gpu backend requested but no GPU is visible")
         from ..ops import native
@@ -247,7 +253,7 @@ class GpuBackend:
                 self._decoder[codec] = GpuHevcDecoder(self.device)
             else:
                 from ..models.h264_decode_gpu import GpuH264Decoder
-                self._decoder[codec] = GpuH264Decoder(self.device)
+                self._decoder[codec] = GpuH264Decoder(self.device, high_depth=self.h264_high_depth)
         return self._decoder[codec]
 
     def decode_streams(self, streams: list[bytes], fps: float = 30.0, keep_high_bit: bool = False):

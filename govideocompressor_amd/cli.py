@@ -79,7 +79,7 @@ def cmd_client(a) -> int:
     from .jobs.worker import Worker, env_config
     conf = env_config()
     gpu = os.environ.get("HIP_VISIBLE_DEVICES", "")
-    be = get_backend(a.backend)
+    be = get_backend(a.backend, h264_high_depth=a.h264_high_depth)
     w = Worker(conf["server_ip"], conf["port"], be, transport.from_env(), leases=a.leases,
                worker_id=os.environ.get("MIVC_WORKER_ID"), gpu=gpu, retry_s=a.retry, heartbeat_s=a.heartbeat,
                idle_exit_s=a.idle_exit, max_jobs=a.max_jobs, out_ext=a.out_ext,
@@ -209,6 +209,8 @@ def build_parser() -> argparse.ArgumentParser:
     cl = sub.add_parser("client", help="pull-based worker (env: SERVER_IP, SERVER_PORT, FTP_USERNAME, FTP_PASSWORD)")
     cl.add_argument("--backend", default=os.environ.get("MIVC_BACKEND", "auto"), choices=["auto", "gpu", "cpu", "ffmpeg"])
     cl.add_argument("--leases", type=int, default=int(os.environ.get("MIVC_LEASES", "1")))
+    cl.add_argument("--h264-high-depth", default=os.environ.get("MIVC_H264_HIGH_DEPTH", "cpu"), choices=["cpu", "gpu"],
+                    help="where 9- / 10-bit H.264 pieces are reconstructed by the gpu backend (default: cpu decoder)")
     cl.add_argument("--retry", type=float, default=float(os.environ.get("MIVC_RETRY_S", "10")))
     cl.add_argument("--heartbeat", type=float, default=5.0)
     cl.add_argument("--idle-exit", type=float, default=None)

@@ -20,12 +20,18 @@ P and B pictures (sub-8x8 partitions, B_8x8, spatial / temporal direct, explicit
 weighted prediction, several references) reconstruct on the GPU; Intra 4x4 / 8x8 / 16x16
 too, I_PCM macroblocks, constrained intra prediction, scaling matrices, and pictures of several
 slices (the records carry each MB's slice for the intra neighbour availability).  Segments the
-GPU path does not cover (High 10 and deeper streams -- the reconstruction kernels are 8-bit --,
-mmco 5, implicit-weighted B slices with more than 8 references in a list, slices of one
+GPU path does not cover (High 10 and deeper streams by default, see below; mmco 5, implicit-weighted B slices with more than 8 references in a list, slices of one
 picture with different reference lists or weights, per-picture filter parameters that differ
 from the batch) are decoded by the CPU decoder instead (``h264_decoder.cc``) and uploaded; the
 result is identical either way (the CPU decoder is the bit-exact oracle of
 ``tests/test_gpu_decode.py``).
+
+High 10: ``GpuH264Decoder(high_depth="gpu")`` reconstructs 9- and 10-bit segments (BitDepthY ==
+BitDepthC) on the GPU too -- ``decode16.hip`` / ``deblock16.hip``, the same records on int16
+planes, in groups of their own beside the 8-bit ones (``tests/test_gpu_decode_high10.py``).
+The option is opt-in until the path has been measured against the CPU decoder
+(``profiles/high10_gpu_decode.md``); the default ``"cpu"`` keeps such segments, and 11- to
+14-bit ones always, on the CPU decoder.
 """
 from __future__ import annotations
 
@@ -47,7 +53,7 @@ class DecodedSegment:
     v: torch.Tensor
     fps: float = 30.0
     path: str = "gpu"  # "gpu" or "cpu" (fallback decoder)
-    # High 10 streams (CPU decoder): int16 planes holding samples of this many bits -- the
+    # High 10 streams (either path): int16 planes holding samples of this many bits -- the
     # layout of the encoders' 10-bit input (models/hevc_gpu.py Main 10)
     bit_depth: int = 8
 
@@ -69,12 +75,23 @@ _META = ("pic_id", "ref_id", "nal_ref", "idr", "slice_type", "slice_qp", "alpha"
 M = {k: i for i, k in enumerate(_META)}
 
 
-def _gpu_plan(seg: dict) -> tuple[bool, str]:
-    """Can the GPU path reconstruct this parsed segment?"""
+# deblock16.hip and decode16.hip keep row progress counters for this many MB rows (kMaxRows)
+_MAX_MB_ROWS_16 = 272
+
+
+def _gpu_plan(seg: dict, high_depth: str = "cpu") -> tuple[bool, str]:
+    """Can the GPU path reconstruct this parsed segment?  ``high_depth="gpu"``: 9- and 10-bit
+    segments too (the parser's ``gpu_ok16``: ``gpu_ok`` but for the bit depth)."""
     if seg.get("error"):
         return False, seg["error"]
     if seg["n"] == 0:
         return False, "no pictures"
+    if high_depth == "gpu" and int(seg["bit_depth"]) > 8:
+        if not np.all(seg["gpu_ok16"] == 1):
+            return False, "unsupported coding tools"
+        if seg["coded_height"] // 16 > _MAX_MB_ROWS_16:
+            return False, "too many macroblock rows"
+        return True, ""
     if not np.all(seg["meta"][:, M["gpu_ok"]] == 1):
         return False, "unsupported coding tools"
     return True, ""
@@ -111,7 +128,12 @@ def dpb_schedule(meta: np.ndarray, lists: np.ndarray):
 class GpuH264Decoder:
     """Decode lists of Annex-B segments into device tensors."""
 
-    def __init__(self, device=None, threads: int | None = None):
+    def __init__(self, device=None, threads: int | None = None, high_depth: str = "cpu"):
+        """``high_depth``: where 9- and 10-bit segments reconstruct -- ``"cpu"`` (the CPU
+        decoder, the default) or ``"gpu"`` (the 16-bit kernels)."""
+        if high_depth not in ("cpu", "gpu"):
+            raise ValueError("high_depth must be 'cpu' or 'gpu'")
+        self.high_depth = high_depth
         if not torch.cuda.is_available():
             raise RuntimeError("GpuH264Decoder needs a GPU")
         self.dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -146,9 +168,9 @@ class GpuH264Decoder:
         out: list[DecodedSegment | None] = [None] * len(segments)
         ok, fallback = [], []
         for i, seg in enumerate(infos):
-            good, why = _gpu_plan(seg)
+            good, why = _gpu_plan(seg, self.high_depth)
             (ok if good else fallback).append(i)
-        # one batch per coded geometry + filter parameters; the rest decode on the CPU
+        # one batch per coded geometry + bit depth + filter parameters; the rest decode on the CPU
         groups: dict[tuple, list[int]] = {}
         for i in ok:
             s = infos[i]
@@ -157,7 +179,8 @@ class GpuH264Decoder:
             if len(params) != 1:
                 fallback.append(i)
                 continue
-            key = (s["coded_width"], s["coded_height"], s["width"], s["height"], s["crop_x"], s["crop_y"], params.pop())
+            key = (s["coded_width"], s["coded_height"], s["width"], s["height"], s["crop_x"], s["crop_y"], params.pop(),
+                   int(s["bit_depth"]))
             groups.setdefault(key, []).append(i)
         self.last_batch = None
         for key, idxs in groups.items():
@@ -213,7 +236,7 @@ class GpuH264Decoder:
         reconstructed straight into their display positions of the output tensors, which are
         also the reference store (no separate decoded picture buffer, no output copy unless
         the stream crops)."""
-        Wc, Hc, w, h, cx, cy, (alpha, beta, cqp, deblock) = key
+        Wc, Hc, w, h, cx, cy, (alpha, beta, cqp, deblock), bd = key
         dev = self.dev
         wmb, hmb = Wc // 16, Hc // 16
         nmb = wmb * hmb
@@ -246,8 +269,10 @@ class GpuH264Decoder:
         # decoded pictures in display order: the output when the stream does not crop, else a
         # coded-size store cropped once at the end
         crop = (Hc, Wc) != (h, w)
-        y_d = torch.empty((B, F, Hc, Wc), dtype=torch.uint8, device=dev)
-        u_d = torch.empty((B, F, Hc // 2, Wc // 2), dtype=torch.uint8, device=dev)
+        # (High 10: int16 planes of bd-bit samples, what the CPU path returns for them)
+        sample = torch.uint8 if bd == 8 else torch.int16
+        y_d = torch.empty((B, F, Hc, Wc), dtype=sample, device=dev)
+        u_d = torch.empty((B, F, Hc // 2, Wc // 2), dtype=sample, device=dev)
         v_d = torch.empty_like(u_d)
         # per step parity: a non-reference step's deblocking (side stream) reads its nz while the
         # next step's reconstruction writes the other
@@ -268,6 +293,25 @@ class GpuH264Decoder:
             consumed[k].record(comp)
         s_ = comp.cuda_stream
         P_ = lambda t: t.data_ptr()  # noqa: E731
+
+        def reconstruct(t, a, any_inter, nz, stream):
+            if bd == 8:
+                self.hip.decode_picture_dpb(B, wmb, hmb, F, P_(y_d), P_(u_d), P_(v_d), P_(d_cur[t]), P_(d_reftab[t]),
+                                            a["wp"], a["sub"], a["hdr"], a["mask"], a["off"], a["coef"], P_(d_run[t]),
+                                            int(any_inter), cqp, P_(nz), P_(err), stream)
+            else:
+                self.hip.decode_picture_dpb16(B, wmb, hmb, F, P_(y_d), P_(u_d), P_(v_d), P_(d_cur[t]),
+                                              P_(d_reftab[t]), a["wp"], a["sub"], a["hdr"], a["mask"], a["off"],
+                                              a["coef"], P_(d_run[t]), int(any_inter), cqp, bd, P_(nz), P_(err), stream)
+
+        def loop_filter(t, a, nz, stream):
+            if bd == 8:
+                self.hip.deblock_dpb(B, wmb, hmb, F, P_(y_d), P_(u_d), P_(v_d), P_(d_cur[t]), a["hdr"], P_(nz),
+                                     a["bs"], cqp, alpha, beta, P_(err), stream)
+            else:
+                self.hip.deblock_dpb16(B, wmb, hmb, F, P_(y_d), P_(u_d), P_(v_d), P_(d_cur[t]), a["hdr"], a["bs"],
+                                       cqp, alpha, beta, bd, P_(err), stream)
+
         for t in range(F):
             k = t & 1
             host_buf, dev_buf = stage[k]
@@ -283,22 +327,18 @@ class GpuH264Decoder:
             a = {n: base + int(L[n]) for n in ("hdr", "mask", "off", "bs", "wp", "coef", "sub")}
             any_inter = bool(np.any(run[t] == 2))
             nz = nzs[k]
-            self.hip.decode_picture_dpb(B, wmb, hmb, F, P_(y_d), P_(u_d), P_(v_d), P_(d_cur[t]), P_(d_reftab[t]),
-                                        a["wp"], a["sub"], a["hdr"], a["mask"], a["off"], a["coef"], P_(d_run[t]),
-                                        int(any_inter), cqp, P_(nz), P_(err), s_)
+            reconstruct(t, a, any_inter, nz, s_)
             if deblock and nonref[t]:
                 # nothing predicts from these pictures: their in-loop filter runs on a side stream
                 # beside the next steps' reconstruction (the step's staging buffer and nz parity are
                 # released after it)
                 decoded[k].record(comp)
                 side.wait_event(decoded[k])
-                self.hip.deblock_dpb(B, wmb, hmb, F, P_(y_d), P_(u_d), P_(v_d), P_(d_cur[t]), a["hdr"], P_(nz),
-                                     a["bs"], cqp, alpha, beta, P_(err), side.cuda_stream)
+                loop_filter(t, a, nz, side.cuda_stream)
                 consumed[k].record(side)
                 continue
             if deblock:
-                self.hip.deblock_dpb(B, wmb, hmb, F, P_(y_d), P_(u_d), P_(v_d), P_(d_cur[t]), a["hdr"], P_(nz),
-                                     a["bs"], cqp, alpha, beta, P_(err), s_)
+                loop_filter(t, a, nz, s_)
             consumed[k].record(comp)
         comp.wait_stream(side)  # the side-stream filters are part of the output
         if crop:
@@ -311,6 +351,6 @@ class GpuH264Decoder:
         if int(err.item()) != 0:
             raise RuntimeError(f"GPU decode failed (err={int(err.item()):#x}: 16 = reference outside the DPB, "
                                "else a wavefront progress timeout)")
-        res = [DecodedSegment(y_out[j, :ns[j]], u_out[j, :ns[j]], v_out[j, :ns[j]], fps, "gpu") for j in range(B)]
+        res = [DecodedSegment(y_out[j, :ns[j]], u_out[j, :ns[j]], v_out[j, :ns[j]], fps, "gpu", bd) for j in range(B)]
         self.last_batch = (y_out, u_out, v_out)
         return res

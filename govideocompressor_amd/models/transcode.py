@@ -26,8 +26,9 @@ import torch
 
 
 class GpuTranscoder:
-    def __init__(self, params, slots: int, device=None, threads: int | None = None):
-        """``params``: H264Params or HevcParams of the output; ``slots``: pieces per GPU batch."""
+    def __init__(self, params, slots: int, device=None, threads: int | None = None, high_depth: str = "cpu"):
+        """``params``: H264Params or HevcParams of the output; ``slots``: pieces per GPU batch;
+        ``high_depth``: where 9- / 10-bit H.264 pieces reconstruct (``GpuH264Decoder``)."""
         from .h264_decode_gpu import GpuH264Decoder
         from .h264_gpu import GpuH264Encoder
         from .hevc_decode_gpu import GpuHevcDecoder
@@ -40,7 +41,7 @@ class GpuTranscoder:
         self.hevc_out = isinstance(params, HevcParams)
         self.enc = (GpuHevcEncoder(params, slots=self.slots, device=self.dev) if self.hevc_out
                     else GpuH264Encoder(params, slots=self.slots, device=self.dev))
-        self.dec = {"h264": GpuH264Decoder(self.dev, threads), "hevc": GpuHevcDecoder(self.dev, threads)}
+        self.dec = {"h264": GpuH264Decoder(self.dev, threads, high_depth=high_depth), "hevc": GpuHevcDecoder(self.dev, threads)}
         self.pool = cf.ThreadPoolExecutor(max_workers=1)
         self.timings: dict[str, float] = {}
 
