@@ -9,6 +9,11 @@
 //   prep_aq_rows      the same offsets written while the source picture is padded to the coded
 //                     size (frame_prep.hip's copy and h264_aq_offsets in one pass: the source
 //                     is read once instead of read, written and read again)
+//   h264_aq_offsets<true>, prep_aq_rows<true>
+//                     x264 --aq-mode 2 / 3 (auto-variance, aq_auto.h): the same two passes over
+//                     the source storing each MB's term a = (energy + 1)^(1/8) as float32
+//   h264_aq_auto_finish  one workgroup per slot that sums the terms of its picture in a fixed
+//                     order and writes the offsets (+ MB-tree, rounding and clamp as above)
 //   h264_qp_flags     per MB: does it carry mb_qp_delta (coded residual, or Intra16x16)?
 //                     (luma from the encoder's non-zero flags, which hold for every MB kind
 //                     but Intra16x16, whose flag is set regardless)
@@ -18,6 +23,7 @@
 //                     every MB) matches a decoder.  Per slot: segmented scan over raster order.
 #include <cmath>
 
+#include "aq_auto.h"
 #include "kcommon.h"
 
 namespace mivc {
@@ -25,14 +31,20 @@ namespace gpu {
 
 using h264::MbHeader;
 
-// The offset of one MB from its sample sums and sums of squares (luma 256, Cb and Cr 64
-// samples each); `extra` (nullable): the MB-tree offset at extra[xi], added before rounding.
-__device__ __forceinline__ int8_t aq_offset(int s, int ss, int cb_s, int cb_ss, int cr_s, int cr_ss, float strength,
-                                            const float* extra, long long xi) {
+// The AC energy of one MB from its sample sums and sums of squares (luma 256, Cb and Cr 64
+// samples each).
+__device__ __forceinline__ uint32_t aq_energy(int s, int ss, int cb_s, int cb_ss, int cr_s, int cr_ss) {
   // the squared luma sum exceeds INT_MAX once the MB mean passes 181: unsigned products
   const uint32_t us = static_cast<uint32_t>(s);
-  const uint32_t e = (static_cast<uint32_t>(ss) - ((us * us) >> 8)) +
-                     static_cast<uint32_t>(cb_ss - ((cb_s * cb_s) >> 6)) + static_cast<uint32_t>(cr_ss - ((cr_s * cr_s) >> 6));
+  return (static_cast<uint32_t>(ss) - ((us * us) >> 8)) + static_cast<uint32_t>(cb_ss - ((cb_s * cb_s) >> 6)) +
+         static_cast<uint32_t>(cr_ss - ((cr_s * cr_s) >> 6));
+}
+
+// The offset of one MB from those sums; `extra` (nullable): the MB-tree offset at extra[xi],
+// added before rounding.
+__device__ __forceinline__ int8_t aq_offset(int s, int ss, int cb_s, int cb_ss, int cr_s, int cr_ss, float strength,
+                                            const float* extra, long long xi) {
+  const uint32_t e = aq_energy(s, ss, cb_s, cb_ss, cr_s, cr_ss);
   float adj = strength * 1.0397f * (log2f(static_cast<float>(e > 1u ? e : 1u)) - 14.427f);
   if (extra) adj += extra[xi];  // MB-tree offset of this frame
   return static_cast<int8_t>(clampi(static_cast<int>(rintf(adj)), -24, 24));
@@ -42,19 +54,22 @@ __device__ __forceinline__ int8_t aq_offset(int s, int ss, int cb_s, int cb_ss, 
 // luma row l (4 dwords) and, for l < 8 Cb row l / for l >= 8 Cr row l - 8 (2 dwords); the
 // group reductions are DPP row sums.  A workgroup walks kAqSpan groups of 16 MBs (one launch
 // of ~nmb / 16 tiny workgroups per slot was dispatch-bound: 0.56 TB/s).
+// kTerm: the auto-variance term pass (h264_aq_offsets<true>) -- `terms` gets aq_term of the MB's
+// energy, and strength, extra, out and rt are not read.
 constexpr int kAqSpan = 8;
 
+template <bool kTerm>
 __global__ __launch_bounds__(256) void h264_aq_offsets(Geom g, const uint8_t* __restrict__ sy,
                                                        const uint8_t* __restrict__ su, const uint8_t* __restrict__ sv,
                                                        float strength, const float* __restrict__ extra,
                                                        long long extra_stride, int8_t* __restrict__ out,
-                                                       const SlotRoute* rt) {
+                                                       const SlotRoute* rt, float* __restrict__ terms) {
   const int l = lane_id() & 15;
   const int nmb = g.nmb();
   const int slot = blockIdx.y;
   // routed: `extra` is the batch's [B, F, nmb] MB-tree table; a slot coding a reference
   // picture takes the row of its display index, other pictures get variance AQ only
-  if (extra && rt) {
+  if (!kTerm && extra && rt) {
     const SlotRoute& r = rt[slot];
     extra = (r.kind >= 0 && r.disp >= 0 && (r.flags & SF_REF)) ? extra + static_cast<size_t>(r.disp) * nmb : nullptr;
   }
@@ -90,8 +105,12 @@ __global__ __launch_bounds__(256) void h264_aq_offsets(Geom g, const uint8_t* __
   s = sum16(s);
   ss = sum16(ss);
   const int cr_s = __shfl(cb_s, (lane_id() & ~15) + 8, 64), cr_ss = __shfl(cb_ss, (lane_id() & ~15) + 8, 64);
-  if (live && l == 0)
-    out[static_cast<size_t>(slot) * nmb + mb] = aq_offset(s, ss, cb_s, cb_ss, cr_s, cr_ss, strength, extra, slot * extra_stride + mb);
+  if (live && l == 0) {
+    if constexpr (kTerm)
+      terms[static_cast<size_t>(slot) * nmb + mb] = aq_term(static_cast<float>(aq_energy(s, ss, cb_s, cb_ss, cr_s, cr_ss)));
+    else
+      out[static_cast<size_t>(slot) * nmb + mb] = aq_offset(s, ss, cb_s, cb_ss, cr_s, cr_ss, strength, extra, slot * extra_stride + mb);
+  }
   }
 }
 
@@ -101,14 +120,17 @@ __global__ __launch_bounds__(256) void h264_aq_offsets(Geom g, const uint8_t* __
 // row.  Every row is loaded once (rows past the display height from its last row), stored
 // to the coded-size planes and summed in place, so an MB's sums live in one lane.  All
 // loads of a plane are issued before its first store (16 x 16 bytes in flight per lane,
-// 1 KiB contiguous per wave and row).  Offsets: aq_offset, as h264_aq_offsets.
+// 1 KiB contiguous per wave and row).  Offsets: aq_offset, as h264_aq_offsets; kTerm: the
+// auto-variance term pass, as there.
 constexpr int kPrepAqWaves = 4;  // MB-row units per workgroup
 
+template <bool kTerm>
 __global__ __launch_bounds__(64 * kPrepAqWaves) void prep_aq_rows(
     const uint8_t* __restrict__ in_y, const uint8_t* __restrict__ in_u, const uint8_t* __restrict__ in_v, int h,
     int64_t in_stride_y, int64_t in_stride_c, const int* __restrict__ fsel, int64_t fstep_y, int64_t fstep_c, Geom g,
     uint8_t* __restrict__ out_y, uint8_t* __restrict__ out_u, uint8_t* __restrict__ out_v, float strength,
-    const float* __restrict__ extra, long long extra_stride, int8_t* __restrict__ out, const SlotRoute* rt) {
+    const float* __restrict__ extra, long long extra_stride, int8_t* __restrict__ out, const SlotRoute* rt,
+    float* __restrict__ terms) {
   const int slot = blockIdx.y;
   const int groups = (g.wmb + 63) >> 6;  // 64-column groups of an MB row
   const int unit = blockIdx.x * kPrepAqWaves + wave_id();
@@ -116,7 +138,7 @@ __global__ __launch_bounds__(64 * kPrepAqWaves) void prep_aq_rows(
   const int my = unit / groups, mx = (unit - my * groups) * 64 + lane_id();
   if (mx >= g.wmb) return;  // no cross-lane step below
   const int nmb = g.nmb(), mb = my * g.wmb + mx;
-  if (extra && rt) {  // as h264_aq_offsets
+  if (!kTerm && extra && rt) {  // as h264_aq_offsets
     const SlotRoute& r = rt[slot];
     extra = (r.kind >= 0 && r.disp >= 0 && (r.flags & SF_REF)) ? extra + static_cast<size_t>(r.disp) * nmb : nullptr;
   }
@@ -157,9 +179,37 @@ __global__ __launch_bounds__(64 * kPrepAqWaves) void prep_aq_rows(
       css[c] = __builtin_amdgcn_udot4(v[r].y, v[r].y, css[c], false);
     }
   }
+  if constexpr (kTerm)
+    terms[static_cast<size_t>(slot) * nmb + mb] =
+        aq_term(static_cast<float>(aq_energy(static_cast<int>(s), static_cast<int>(ss), static_cast<int>(cs[0]),
+                                             static_cast<int>(css[0]), static_cast<int>(cs[1]), static_cast<int>(css[1]))));
+  else
   out[static_cast<size_t>(slot) * nmb + mb] = aq_offset(static_cast<int>(s), static_cast<int>(ss), static_cast<int>(cs[0]),
                                                         static_cast<int>(css[0]), static_cast<int>(cs[1]),
                                                         static_cast<int>(css[1]), strength, extra, slot * extra_stride + mb);
+}
+
+// The finish pass of auto-variance AQ (aq_auto.h): workgroup `slot` reads the nmb terms of its
+// picture twice (the second time from cache) and nothing else of the source.  extra,
+// extra_stride, rt: as h264_aq_offsets.
+__global__ __launch_bounds__(kAqFinishThreads) void h264_aq_auto_finish(int nmb, const float* __restrict__ terms,
+                                                                        int mode, float strength,
+                                                                        const float* __restrict__ extra,
+                                                                        long long extra_stride,
+                                                                        int8_t* __restrict__ out, const SlotRoute* rt) {
+  __shared__ double red[2 * kAqFinishThreads];
+  const int slot = blockIdx.x;
+  if (extra && rt) {
+    const SlotRoute& r = rt[slot];
+    extra = (r.kind >= 0 && r.disp >= 0 && (r.flags & SF_REF)) ? extra + static_cast<size_t>(r.disp) * nmb : nullptr;
+  }
+  const float* t = terms + static_cast<size_t>(slot) * nmb;
+  const AqAutoStats st = aq_auto_stats(t, nmb, mode, strength, red);
+  for (int i = threadIdx.x; i < nmb; i += kAqFinishThreads) {
+    float adj = aq_auto_adj(st, t[i]);
+    if (extra) adj += extra[slot * extra_stride + i];
+    out[static_cast<size_t>(slot) * nmb + i] = static_cast<int8_t>(clampi(static_cast<int>(rintf(adj)), -24, 24));
+  }
 }
 
 // 16 lanes per MB (16 MBs per 256-thread workgroup).  The MB carries mb_qp_delta iff it
@@ -248,9 +298,37 @@ extern "C" void mivc_launch_aq_offsets(int B, int wmb, int hmb, const uint8_t* s
                                        const uint8_t* sv, float strength, const float* extra, long long extra_stride,
                                        int8_t* out, void* stream, const void* route) {
   const Geom g{B, wmb, hmb, wmb * 16, hmb * 16};
-  hipLaunchKernelGGL(h264_aq_offsets, dim3((wmb * hmb + 16 * kAqSpan - 1) / (16 * kAqSpan), B), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), g,
-                     sy, su, sv, strength, extra, extra_stride, out, static_cast<const SlotRoute*>(route));
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(h264_aq_offsets<false>), dim3((wmb * hmb + 16 * kAqSpan - 1) / (16 * kAqSpan), B),
+                     dim3(256), 0, static_cast<hipStream_t>(stream), g, sy, su, sv, strength, extra, extra_stride, out,
+                     static_cast<const SlotRoute*>(route), static_cast<float*>(nullptr));
+}
+
+extern "C" void mivc_launch_aq_terms(int B, int wmb, int hmb, const uint8_t* sy, const uint8_t* su, const uint8_t* sv,
+                                     float* terms, void* stream) {
+  const Geom g{B, wmb, hmb, wmb * 16, hmb * 16};
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(h264_aq_offsets<true>), dim3((wmb * hmb + 16 * kAqSpan - 1) / (16 * kAqSpan), B),
+                     dim3(256), 0, static_cast<hipStream_t>(stream), g, sy, su, sv, 0.0f,
+                     static_cast<const float*>(nullptr), 0LL, static_cast<int8_t*>(nullptr),
+                     static_cast<const SlotRoute*>(nullptr), terms);
+}
+
+// mode: 2 (auto-variance) or 3 (with the dark-scene bias); terms: [B, nmb] of a term launch
+extern "C" void mivc_launch_aq_auto_finish(int B, int nmb, const float* terms, int mode, float strength,
+                                           const float* extra, long long extra_stride, int8_t* out, void* stream,
+                                           const void* route) {
+  hipLaunchKernelGGL(h264_aq_auto_finish, dim3(B), dim3(kAqFinishThreads), 0, static_cast<hipStream_t>(stream), nmb,
+                     terms, mode, strength, extra, extra_stride, out, static_cast<const SlotRoute*>(route));
+}
+
+// the shapes and pointers prep_aq_rows takes
+static bool prep_aq_fast(const uint8_t* in_y, const uint8_t* in_u, const uint8_t* in_v, int w, int h,
+                         int64_t in_stride_y, int64_t in_stride_c, const uint8_t* out_y, const uint8_t* out_u,
+                         const uint8_t* out_v, int W, int H) {
+  auto al = [](const void* p, uintptr_t n) { return reinterpret_cast<uintptr_t>(p) % n == 0; };
+  const int64_t fstep_y = static_cast<int64_t>(w) * h, fstep_c = static_cast<int64_t>(w / 2) * (h / 2);
+  return w == W && W % 16 == 0 && H % 16 == 0 && h % 2 == 0 && h >= 2 && h <= H && in_stride_y % 16 == 0 &&
+         in_stride_c % 8 == 0 && fstep_y % 16 == 0 && fstep_c % 8 == 0 && al(in_y, 16) && al(in_u, 8) && al(in_v, 8) &&
+         al(out_y, 16) && al(out_u, 8) && al(out_v, 8);
 }
 
 // Pad frame fsel[slot] (nullable: frame 0) of every slot's clip to the coded size and write its
@@ -261,18 +339,33 @@ extern "C" int mivc_launch_prep_aq(const uint8_t* in_y, const uint8_t* in_u, con
                                    int64_t in_stride_y, int64_t in_stride_c, int B, uint8_t* out_y, uint8_t* out_u,
                                    uint8_t* out_v, int W, int H, const int* fsel, float strength, const float* extra,
                                    long long extra_stride, int8_t* out, void* stream, const void* route) {
-  auto al = [](const void* p, uintptr_t n) { return reinterpret_cast<uintptr_t>(p) % n == 0; };
   const int64_t fstep_y = static_cast<int64_t>(w) * h, fstep_c = static_cast<int64_t>(w / 2) * (h / 2);
-  const bool fast = w == W && W % 16 == 0 && H % 16 == 0 && h % 2 == 0 && h >= 2 && h <= H && strength > 0.f &&
-                    in_stride_y % 16 == 0 && in_stride_c % 8 == 0 && fstep_y % 16 == 0 && fstep_c % 8 == 0 &&
-                    al(in_y, 16) && al(in_u, 8) && al(in_v, 8) && al(out_y, 16) && al(out_u, 8) && al(out_v, 8);
+  const bool fast = strength > 0.f && prep_aq_fast(in_y, in_u, in_v, w, h, in_stride_y, in_stride_c, out_y, out_u, out_v, W, H);
   if (!fast) return 0;
   const Geom g{B, W / 16, H / 16, W, H};
   const int units = g.hmb * ((g.wmb + 63) / 64);
-  hipLaunchKernelGGL(prep_aq_rows, dim3((units + kPrepAqWaves - 1) / kPrepAqWaves, B), dim3(64 * kPrepAqWaves), 0,
-                     static_cast<hipStream_t>(stream), in_y, in_u, in_v, h, in_stride_y, in_stride_c, fsel, fstep_y,
-                     fstep_c, g, out_y, out_u, out_v, strength, extra, extra_stride, out,
-                     static_cast<const SlotRoute*>(route));
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(prep_aq_rows<false>), dim3((units + kPrepAqWaves - 1) / kPrepAqWaves, B),
+                     dim3(64 * kPrepAqWaves), 0, static_cast<hipStream_t>(stream), in_y, in_u, in_v, h, in_stride_y,
+                     in_stride_c, fsel, fstep_y, fstep_c, g, out_y, out_u, out_v, strength, extra, extra_stride, out,
+                     static_cast<const SlotRoute*>(route), static_cast<float*>(nullptr));
+  return 1;
+}
+
+// mivc_launch_prep_aq for auto-variance AQ: the planes as there, the terms ([B, nmb] float32)
+// instead of the offsets.  The same fast path and return value; the caller's other route is
+// mivc_launch_prep and mivc_launch_aq_terms.
+extern "C" int mivc_launch_prep_aq_terms(const uint8_t* in_y, const uint8_t* in_u, const uint8_t* in_v, int w, int h,
+                                         int64_t in_stride_y, int64_t in_stride_c, int B, uint8_t* out_y,
+                                         uint8_t* out_u, uint8_t* out_v, int W, int H, const int* fsel, float* terms,
+                                         void* stream) {
+  if (!prep_aq_fast(in_y, in_u, in_v, w, h, in_stride_y, in_stride_c, out_y, out_u, out_v, W, H)) return 0;
+  const int64_t fstep_y = static_cast<int64_t>(w) * h, fstep_c = static_cast<int64_t>(w / 2) * (h / 2);
+  const Geom g{B, W / 16, H / 16, W, H};
+  const int units = g.hmb * ((g.wmb + 63) / 64);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(prep_aq_rows<true>), dim3((units + kPrepAqWaves - 1) / kPrepAqWaves, B),
+                     dim3(64 * kPrepAqWaves), 0, static_cast<hipStream_t>(stream), in_y, in_u, in_v, h, in_stride_y,
+                     in_stride_c, fsel, fstep_y, fstep_c, g, out_y, out_u, out_v, 0.0f, static_cast<const float*>(nullptr),
+                     0LL, static_cast<int8_t*>(nullptr), static_cast<const SlotRoute*>(nullptr), terms);
   return 1;
 }
 

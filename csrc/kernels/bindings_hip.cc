@@ -75,6 +75,13 @@ int mivc_launch_prep_aq(const uint8_t* in_y, const uint8_t* in_u, const uint8_t*
                         int64_t in_stride_c, int B, uint8_t* out_y, uint8_t* out_u, uint8_t* out_v, int W, int H,
                         const int* fsel, float strength, const float* extra, long long extra_stride, int8_t* out,
                         void* stream, const void* route);
+void mivc_launch_aq_terms(int B, int wmb, int hmb, const uint8_t* sy, const uint8_t* su, const uint8_t* sv, float* terms,
+                          void* stream);
+void mivc_launch_aq_auto_finish(int B, int nmb, const float* terms, int mode, float strength, const float* extra,
+                                long long extra_stride, int8_t* out, void* stream, const void* route);
+int mivc_launch_prep_aq_terms(const uint8_t* in_y, const uint8_t* in_u, const uint8_t* in_v, int w, int h,
+                              int64_t in_stride_y, int64_t in_stride_c, int B, uint8_t* out_y, uint8_t* out_u,
+                              uint8_t* out_v, int W, int H, const int* fsel, float* terms, void* stream);
 void mivc_launch_me_halfpel(int B, int W, int H, const uint8_t* ref_y, uint8_t* hp, void* stream, const void* route,
                             int nbuf);
 void mivc_launch_encode_inter(int B, int wmb, int hmb, const uint8_t* src_y, const uint8_t* src_u,
@@ -154,6 +161,11 @@ void mivc_launch_hevc_pack_levels(int B, int W, int H, const int16_t* cy, const 
 void mivc_launch_hevc_merge_refine(int B, int wmb, int hmb, const uint8_t* src_y, const uint8_t* ref, const uint8_t* hp,
                                    const int16_t* mv_in, int16_t* mv_out, int* cost, const int16_t* pm, const int* qp,
                                    const int8_t* aq, void* stream);
+void mivc_launch_hevc_aq_terms(int B, int W, int H, int bd, const uint16_t* sy, const uint16_t* su, const uint16_t* sv,
+                               float* terms, void* stream);
+void mivc_launch_hevc_aq_auto_finish(int B, int W, int H, const float* terms, const int* qp, int mode, float strength,
+                                     const float* extra, long long extra_stride, int extra_rows, int* ctb_qp,
+                                     int8_t* mb_aq, void* stream);
 void mivc_launch_hevc_qp_fixup(int B, int W, int H, void* ctu, const void* cu, const int* qp, const int8_t* run,
                                int wpp, void* stream, int ctu64);
 void mivc_launch_hevc_sao(int B, int W, int H, int bd, const uint16_t* dy, const uint16_t* du, const uint16_t* dv,
@@ -393,6 +405,37 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("iy"), py::arg("iu"), py::arg("iv"), py::arg("w"), py::arg("h"), py::arg("sy"), py::arg("sc"), py::arg("n"),
      py::arg("oy"), py::arg("ou"), py::arg("ov"), py::arg("W"), py::arg("H"), py::arg("strength"), py::arg("out"),
      py::arg("stream"), py::arg("fsel") = 0, py::arg("extra") = 0, py::arg("extra_stride") = 0, py::arg("route") = 0);
+  // auto-variance AQ (x264 --aq-mode 2 / 3, aq_auto.h): the term passes store (energy + 1)^(1/8)
+  // of every MB as float32 [B, nmb] (aq_terms: from the coded planes; prep_aq_terms: with the
+  // padding, prep_aq's fast path and return value), aq_auto_finish turns a term buffer into the
+  // int8 offsets (extra / extra_stride / route as aq_offsets)
+  m.def("aq_terms", [](int B, int wmb, int hmb, uintptr_t sy, uintptr_t su, uintptr_t sv, uintptr_t terms,
+                       uintptr_t stream) {
+    if (B < 1 || wmb < 1 || hmb < 1) throw std::invalid_argument("aq_terms: bad geometry");
+    if (!sy || !su || !sv || !terms) throw std::invalid_argument("aq_terms: needs the planes and the term buffer");
+    mivc_launch_aq_terms(B, wmb, hmb, P<uint8_t>(sy), P<uint8_t>(su), P<uint8_t>(sv), P<float>(terms), S(stream));
+  }, py::arg("B"), py::arg("wmb"), py::arg("hmb"), py::arg("sy"), py::arg("su"), py::arg("sv"), py::arg("terms"),
+     py::arg("stream"));
+  m.def("prep_aq_terms", [](uintptr_t iy, uintptr_t iu, uintptr_t iv, int w, int h, int64_t sy, int64_t sc, int n,
+                            uintptr_t oy, uintptr_t ou, uintptr_t ov, int W, int H, uintptr_t terms, uintptr_t stream,
+                            uintptr_t fsel) {
+    if (W < w || H < h || w < 2 || h < 2 || n < 1) throw std::invalid_argument("prep_aq_terms: bad geometry");
+    if (!terms) throw std::invalid_argument("prep_aq_terms: needs the term buffer");
+    return mivc_launch_prep_aq_terms(P<uint8_t>(iy), P<uint8_t>(iu), P<uint8_t>(iv), w, h, sy, sc, n, P<uint8_t>(oy),
+                                     P<uint8_t>(ou), P<uint8_t>(ov), W, H, P<int>(fsel), P<float>(terms),
+                                     S(stream)) != 0;
+  }, py::arg("iy"), py::arg("iu"), py::arg("iv"), py::arg("w"), py::arg("h"), py::arg("sy"), py::arg("sc"), py::arg("n"),
+     py::arg("oy"), py::arg("ou"), py::arg("ov"), py::arg("W"), py::arg("H"), py::arg("terms"), py::arg("stream"),
+     py::arg("fsel") = 0);
+  m.def("aq_auto_finish", [](int B, int nmb, uintptr_t terms, int mode, float strength, uintptr_t out, uintptr_t stream,
+                             uintptr_t extra, long long extra_stride, uintptr_t route) {
+    if (B < 1 || nmb < 1) throw std::invalid_argument("aq_auto_finish: bad geometry");
+    if (mode != 2 && mode != 3) throw std::invalid_argument("aq_auto_finish: mode must be 2 or 3");
+    if (!terms || !out) throw std::invalid_argument("aq_auto_finish: needs the term and the offset buffer");
+    mivc_launch_aq_auto_finish(B, nmb, P<float>(terms), mode, strength, P<float>(extra), extra_stride, P<int8_t>(out),
+                               S(stream), P<void>(route));
+  }, py::arg("B"), py::arg("nmb"), py::arg("terms"), py::arg("mode"), py::arg("strength"), py::arg("out"),
+     py::arg("stream"), py::arg("extra") = 0, py::arg("extra_stride") = 0, py::arg("route") = 0);
   m.def("me_halfpel", [](int B, int W, int H, uintptr_t ref, uintptr_t hp, uintptr_t stream, uintptr_t route, int nbuf) {
     if (route && nbuf < 1) throw std::invalid_argument("me_halfpel: a routed launch needs the pool size");
     mivc_launch_me_halfpel(B, W, H, P<uint8_t>(ref), P<uint8_t>(hp), S(stream), P<void>(route), nbuf);
@@ -642,6 +685,28 @@ PYBIND11_MODULE(_hip, m) {
     if (extra && (extra_rows < 0 || extra_rows > H / 16)) throw std::invalid_argument("hevc_aq: extra_rows out of range");
     mivc_launch_hevc_aq(B, W, H, bd, P<uint16_t>(sy), P<uint16_t>(su), P<uint16_t>(sv), P<int>(qp), strength,
                         P<float>(extra), extra_stride, extra_rows, P<int>(ctb_qp), P<int8_t>(mb_aq), S(stream));
+  });
+  // auto-variance AQ (aq_auto.h): hevc_aq_terms stores (energy / 4^(bd - 8) + 1)^(1/8) of every
+  // 16x16 block as float32 [B, nmb16]; hevc_aq_auto_finish writes what hevc_aq writes from them
+  m.def("hevc_aq_terms", [](int B, int W, int H, int bd, uintptr_t sy, uintptr_t su, uintptr_t sv, uintptr_t terms,
+                            uintptr_t stream) {
+    if (B < 1 || W < 32 || H < 32 || (W & 31) || (H & 31))
+      throw std::invalid_argument("hevc_aq_terms: coded size must be a multiple of 32");
+    if (bd < 8 || bd > 12) throw std::invalid_argument("hevc_aq_terms: bit depth 8..12");
+    if (!sy || !su || !sv || !terms) throw std::invalid_argument("hevc_aq_terms: needs the planes and the term buffer");
+    mivc_launch_hevc_aq_terms(B, W, H, bd, P<uint16_t>(sy), P<uint16_t>(su), P<uint16_t>(sv), P<float>(terms), S(stream));
+  });
+  m.def("hevc_aq_auto_finish", [](int B, int W, int H, uintptr_t terms, uintptr_t qp, int mode, float strength,
+                                  uintptr_t extra, long long extra_stride, int extra_rows, uintptr_t ctb_qp,
+                                  uintptr_t mb_aq, uintptr_t stream) {
+    if (B < 1 || W < 32 || H < 32 || (W & 31) || (H & 31))
+      throw std::invalid_argument("hevc_aq_auto_finish: coded size must be a multiple of 32");
+    if (mode != 2 && mode != 3) throw std::invalid_argument("hevc_aq_auto_finish: mode must be 2 or 3");
+    if (!terms || !qp || !ctb_qp) throw std::invalid_argument("hevc_aq_auto_finish: needs the terms, the slot QPs and ctb_qp");
+    if (extra && (extra_rows < 0 || extra_rows > H / 16))
+      throw std::invalid_argument("hevc_aq_auto_finish: extra_rows out of range");
+    mivc_launch_hevc_aq_auto_finish(B, W, H, P<float>(terms), P<int>(qp), mode, strength, P<float>(extra), extra_stride,
+                                    extra_rows, P<int>(ctb_qp), P<int8_t>(mb_aq), S(stream));
   });
   m.def("hevc_pack_levels", [](int B, int W, int H, uintptr_t cy, uintptr_t cb, uintptr_t cr, uintptr_t nzmap,
                                uintptr_t cnt, uintptr_t off, long long cap_blocks, uintptr_t out, uintptr_t err,

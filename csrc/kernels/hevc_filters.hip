@@ -12,6 +12,7 @@
 // CTB gathers edge-/band-offset statistics against the source in LDS, picks the
 // cheapest of {off, 4 edge classes, band} per component with an SSE + lambda * bits
 // estimate, stores the parameters for the CABAC writer and applies them.
+#include "aq_auto.h"
 #include "kcommon.h"
 #include "../common/hevc_tables.h"
 
@@ -734,13 +735,15 @@ __global__ __launch_bounds__(256) void hevc_sao_apply(HevcSaoArgs a) {
 // float offset, e.g. MB-tree); the CTB's QP offset is the rounded mean of its four
 // blocks (x265 averages the AQ partitions of a quantization group), clamped to +-12 so
 // that consecutive CTBs stay within CuQpDeltaVal's range.  One wave per 16x16 block.
-__global__ __launch_bounds__(256) void hevc_aq_ctb(int W, int H, int bd, const uint16_t* __restrict__ sy,
-                                                   const uint16_t* __restrict__ su, const uint16_t* __restrict__ sv,
-                                                   const int* __restrict__ qp, float strength,
-                                                   const float* __restrict__ extra, long long extra_stride,
-                                                   int extra_rows, int* __restrict__ ctb_qp,
-                                                   int8_t* __restrict__ mb_aq) {
-  __shared__ float s_off[4];
+// kTerm: the term pass of auto-variance AQ (--aq-mode 2 / 3, aq_auto.h) -- `terms` ([B, nmb16]
+// float32) gets aq_term of each block's energy at 8-bit scale; hevc_aq_auto_finish does the rest.
+template <bool kTerm>
+__device__ __forceinline__ void hevc_aq_body(int W, int H, int bd, const uint16_t* __restrict__ sy,
+                                             const uint16_t* __restrict__ su, const uint16_t* __restrict__ sv,
+                                             const int* __restrict__ qp, float strength,
+                                             const float* __restrict__ extra, long long extra_stride, int extra_rows,
+                                             int* __restrict__ ctb_qp, int8_t* __restrict__ mb_aq, float* s_off,
+                                             float* __restrict__ terms) {
   const int wctb = W / 32, nctb = wctb * (H / 32), wmb = W / 16, nmb = wmb * (H / 16);
   const int ci = blockIdx.x, slot = blockIdx.y;
   const int q = wave_id(), l = lane_id();
@@ -759,12 +762,17 @@ __global__ __launch_bounds__(256) void hevc_aq_ctb(int W, int H, int bd, const u
   if (l == 0) {
     const long long e = (ss - ((static_cast<long long>(s) * s) >> 8)) + (css - ((static_cast<long long>(cs) * cs) >> 6)) +
                         (css_v - ((static_cast<long long>(cs_v) * cs_v) >> 6));
+    if constexpr (kTerm) {
+      terms[static_cast<size_t>(slot) * nmb + my * wmb + mx] = aq_term(ldexpf(static_cast<float>(e), -2 * (bd - 8)));
+    } else {
     float adj = 0.0f;
     if (strength > 0.0f)
       adj = strength * 1.0397f * (log2f(static_cast<float>(e > 1 ? e : 1)) - (14.427f + 2.0f * (bd - 8)));
     if (extra && my < extra_rows) adj += extra[slot * extra_stride + my * wmb + mx];
     s_off[q] = adj;
+    }
   }
+  if constexpr (kTerm) return;
   __syncthreads();
   if (threadIdx.x == 0) {
     const int off = clampi(static_cast<int>(rintf(0.25f * (s_off[0] + s_off[1] + s_off[2] + s_off[3]))), -12, 12);
@@ -775,6 +783,57 @@ __global__ __launch_bounds__(256) void hevc_aq_ctb(int W, int H, int bd, const u
       const int r0 = (ci / wctb) * 2, c0i = (ci % wctb) * 2;
       int8_t* m = mb_aq + static_cast<size_t>(slot) * nmb;
       m[r0 * wmb + c0i] = m[r0 * wmb + c0i + 1] = m[(r0 + 1) * wmb + c0i] = m[(r0 + 1) * wmb + c0i + 1] =
+          static_cast<int8_t>(v - base);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void hevc_aq_ctb(int W, int H, int bd, const uint16_t* __restrict__ sy,
+                                                   const uint16_t* __restrict__ su, const uint16_t* __restrict__ sv,
+                                                   const int* __restrict__ qp, float strength,
+                                                   const float* __restrict__ extra, long long extra_stride,
+                                                   int extra_rows, int* __restrict__ ctb_qp,
+                                                   int8_t* __restrict__ mb_aq) {
+  __shared__ float s_off[4];
+  hevc_aq_body<false>(W, H, bd, sy, su, sv, qp, strength, extra, extra_stride, extra_rows, ctb_qp, mb_aq, s_off, nullptr);
+}
+
+__global__ __launch_bounds__(256) void hevc_aq_terms(int W, int H, int bd, const uint16_t* __restrict__ sy,
+                                                     const uint16_t* __restrict__ su, const uint16_t* __restrict__ sv,
+                                                     float* __restrict__ terms) {
+  hevc_aq_body<true>(W, H, bd, sy, su, sv, nullptr, 0.0f, nullptr, 0, 0, nullptr, nullptr, nullptr, terms);
+}
+
+// The finish pass of auto-variance AQ (aq_auto.h): workgroup `slot` sums its picture's terms,
+// then a thread per CTB averages the unrounded offsets (+ `extra` in rows below extra_rows) of
+// its four blocks and writes the CTB's QP and mb_aq as hevc_aq_ctb does.
+__global__ __launch_bounds__(kAqFinishThreads) void hevc_aq_auto_finish(int W, int H, const float* __restrict__ terms,
+                                                                        const int* __restrict__ qp, int mode,
+                                                                        float strength, const float* __restrict__ extra,
+                                                                        long long extra_stride, int extra_rows,
+                                                                        int* __restrict__ ctb_qp,
+                                                                        int8_t* __restrict__ mb_aq) {
+  __shared__ double red[2 * kAqFinishThreads];
+  const int wctb = W / 32, nctb = wctb * (H / 32), wmb = W / 16, nmb = wmb * (H / 16);
+  const int slot = blockIdx.x;
+  const float* t = terms + static_cast<size_t>(slot) * nmb;
+  const AqAutoStats st = aq_auto_stats(t, nmb, mode, strength, red);
+  const int base = qp[slot];
+  for (int ci = threadIdx.x; ci < nctb; ci += kAqFinishThreads) {
+    const int r0 = (ci / wctb) * 2, c0 = (ci % wctb) * 2;
+    float off[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int my = r0 + (q >> 1), mx = c0 + (q & 1);
+      off[q] = aq_auto_adj(st, t[my * wmb + mx]);
+      if (extra && my < extra_rows) off[q] += extra[slot * extra_stride + my * wmb + mx];
+    }
+    const int o = clampi(static_cast<int>(rintf(0.25f * (off[0] + off[1] + off[2] + off[3]))), -12, 12);
+    const int v = clampi(base + o, 0, 51);
+    ctb_qp[static_cast<size_t>(slot) * nctb + ci] = v;
+    if (mb_aq) {
+      int8_t* m = mb_aq + static_cast<size_t>(slot) * nmb;
+      m[r0 * wmb + c0] = m[r0 * wmb + c0 + 1] = m[(r0 + 1) * wmb + c0] = m[(r0 + 1) * wmb + c0 + 1] =
           static_cast<int8_t>(v - base);
     }
   }
@@ -1037,6 +1096,21 @@ extern "C" void mivc_launch_hevc_aq(int B, int W, int H, int bd, const uint16_t*
                                     long long extra_stride, int extra_rows, int* ctb_qp, int8_t* mb_aq, void* stream) {
   hipLaunchKernelGGL(hevc_aq_ctb, dim3((W / 32) * (H / 32), B), dim3(256), 0, static_cast<hipStream_t>(stream), W, H,
                      bd, sy, su, sv, qp, strength, extra, extra_stride, extra_rows, ctb_qp, mb_aq);
+}
+
+// auto-variance AQ (aq_auto.h): terms [B, nmb16] float32; the finish launch's other arguments
+// as mivc_launch_hevc_aq, mode 2 or 3
+extern "C" void mivc_launch_hevc_aq_terms(int B, int W, int H, int bd, const uint16_t* sy, const uint16_t* su,
+                                          const uint16_t* sv, float* terms, void* stream) {
+  hipLaunchKernelGGL(hevc_aq_terms, dim3((W / 32) * (H / 32), B), dim3(256), 0, static_cast<hipStream_t>(stream), W, H,
+                     bd, sy, su, sv, terms);
+}
+
+extern "C" void mivc_launch_hevc_aq_auto_finish(int B, int W, int H, const float* terms, const int* qp, int mode,
+                                                float strength, const float* extra, long long extra_stride,
+                                                int extra_rows, int* ctb_qp, int8_t* mb_aq, void* stream) {
+  hipLaunchKernelGGL(hevc_aq_auto_finish, dim3(B), dim3(kAqFinishThreads), 0, static_cast<hipStream_t>(stream), W, H,
+                     terms, qp, mode, strength, extra, extra_stride, extra_rows, ctb_qp, mb_aq);
 }
 
 extern "C" void mivc_launch_hevc_qp_fixup(int B, int W, int H, void* ctu, const void* cu, const int* qp,

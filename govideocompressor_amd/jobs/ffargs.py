@@ -154,6 +154,16 @@ def _aq_mode(v: str) -> float | None:
     raise FfArgsError(f"aq-mode {m}: only 0 (off) and 1 (variance AQ) are implemented")
 
 
+def _aq_mode_hevc(v: str) -> dict:
+    """x265 aq-mode -> knob overrides (a '*' destination): 0 turns the strength off, as it always
+    did; 1 .. 3 select HevcParams.aq_mode."""
+    m = int(v)
+    if m not in (0, 1, 2, 3):
+        raise FfArgsError(f"aq-mode {m}: implemented are 0 (off), 1 (variance AQ), 2 (auto-variance) and "
+                          f"3 (auto-variance with a dark-scene bias)")
+    return dict(aq_strength=0.0) if m == 0 else dict(aq_mode=m)
+
+
 def _subme(v: str) -> int:
     m = int(v)
     if m < 0 or m > 11:
@@ -181,7 +191,8 @@ def _partitions(v: str) -> bool:
 
 
 # -x264-params keys -> (H264Params field | EncoderConfig attribute prefixed '@', converter).
-# A converter result of None leaves the field at its preset value.
+# A converter result of None leaves the field at its preset value; the destination '*' takes a
+# dict of field overrides.
 H264_PARAMS = {
     "bframes": ("bframes", _int_in(0, 3)),
     "keyint": ("@keyint", _int_in(1, 100000)),
@@ -223,7 +234,7 @@ HEVC_PARAMS = {
     "tmvp": ("tmvp", _flag),
     "no-tmvp": ("tmvp", lambda v: not _flag(v)),
     "keyint": ("@keyint", _int_in(1, 100000)),
-    "aq-mode": ("aq_strength", _aq_mode),
+    "aq-mode": ("*", _aq_mode_hevc),
     "aq-strength": ("aq_strength", _float_in(0.0, 3.0)),
     "cutree": ("cutree", _flag),
     "no-cutree": ("cutree", lambda v: not _flag(v)),
@@ -253,7 +264,7 @@ _HEVC_PROFILES = {"main": {}, "main10": {}, "mainstillpicture": dict(intra_only=
 _TUNES = {
     "h264": {"psnr": dict(aq_strength=0.0), "zerolatency": dict(bframes=0, lookahead=False, mbtree=False),
              "fastdecode": dict(cabac=False, deblock=False)},
-    "hevc": {"psnr": dict(aq_strength=0.0), "zerolatency": dict(bframes=0, lookahead=False, cutree=False),
+    "hevc": {"psnr": dict(aq_strength=0.0), "ssim": dict(aq_mode=2), "zerolatency": dict(bframes=0, lookahead=False, cutree=False),
              "fastdecode": dict(deblock=False, sao=False)},
 }
 
@@ -443,7 +454,9 @@ def _codec_options(cfg: EncoderConfig, codec_params: list[tuple[str, str]]) -> b
                 raise FfArgsError(f"{flag} {k}: {e}") from None
             except ValueError:
                 raise FfArgsError(f"{flag} {k}: bad value {v!r}") from None
-            if dest.startswith("@"):
+            if dest == "*":
+                cfg.opts.update(x)
+            elif dest.startswith("@"):
                 attr = dest[1:]
                 if attr == "keyint":
                     cfg.keyint = x

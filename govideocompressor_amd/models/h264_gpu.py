@@ -86,6 +86,15 @@ class H264Params:
     # x264 --aq-mode 1 (variance AQ): per-MB QP offset strength * 1.0397 * (log2(AC energy)
     # - 14.427); 0 disables (every MB at the frame QP)
     aq_strength: float = 1.0
+    # x264 --aq-mode: 0 off (as aq_strength 0), 1 the rule above, 2 auto-variance, 3 auto-variance
+    # with a dark-scene bias.  2 / 3 take a = (AC energy + 1)^(1/8) per MB and the statistics of
+    # the MB's own coded picture, m = mean a, avg = m - 0.5 (mean a^2 - 14) / m: offset =
+    # strength * m * (a - avg) [+ strength * (1 - 14 / a^2) in mode 3], then MB-tree, rounding and
+    # the +-24 clamp as in mode 1 (csrc/kernels/aq_auto.h: a term pass and one workgroup per slot
+    # that sums in a fixed order, so the bytes stay reproducible).  Measured against mode 1
+    # (profiles/aq_auto_variance.md): headline -2.3 % fps (mode 2) / -2.7 % (mode 3); content suite
+    # BD-rate mode 2 +0.21 % on PSNR-Y, -0.94 % on SSIM-Y; mode 3 +1.90 %, -0.08 % -- opt-in
+    aq_mode: int = 1
     # x264 --mbtree (default on): lookahead propagation of inter-frame references -> per-MB
     # QP offsets (csrc/kernels/mbtree.hip), with x264's CRF compensation; needs the lookahead
     mbtree: bool = True
@@ -421,6 +430,8 @@ class GpuH264Encoder:
             raise ValueError("direct must be 'temporal' or 'spatial'")
         if entropy not in ("gpu", "cpu"):
             raise ValueError("entropy must be 'gpu' or 'cpu'")
+        if isinstance(params.aq_mode, bool) or params.aq_mode not in (0, 1, 2, 3):
+            raise ValueError("aq_mode must be 0 (off), 1 (variance), 2 (auto-variance) or 3 (auto-variance, biased)")
         if params.eff_slices() > 1 and params.direct == "spatial" and params.eff_bframes() and params.spatial_wavefront:
             raise ValueError("slices > 1: spatial direct needs the fast path (spatial_wavefront=False)")
         self.entropy = entropy
@@ -431,6 +442,12 @@ class GpuH264Encoder:
         self.dev = _resolve(device)
         self.hip = native.hip()
         self.host = native.host()
+        # AQ as the kernels see it: aq_mode 0 is strength 0; auto-variance (2 / 3) only shapes the
+        # variance part, so without one (strength 0, MB-tree alone) the mode-1 launches run
+        self.aq_strength = float(params.aq_strength) if params.aq_mode else 0.0
+        self.aq_auto = int(params.aq_mode) if (params.aq_mode in (2, 3) and self.aq_strength > 0) else 0
+        if self.aq_auto and not hasattr(self.hip, "aq_auto_finish"):
+            raise RuntimeError("aq_mode 2 / 3 need a kernel library with the auto-variance AQ kernels (rebuild)")
         self.wmb = (params.width + 15) // 16
         self.hmb = (params.height + 15) // 16
         self.W, self.H = self.wmb * 16, self.hmb * 16
@@ -506,6 +523,8 @@ class GpuH264Encoder:
             self.src_me = torch.zeros((B, H, W), dtype=u8, device=dev)  # inverse-weighted luma for ME
         self.intra_flag = torch.zeros((B, nmb), dtype=u8, device=dev)
         self.aq = torch.zeros((B, nmb), dtype=torch.int8, device=dev)     # per-MB QP offsets (AQ)
+        if self.aq_auto:
+            self.aq_terms = torch.zeros((B, nmb), dtype=torch.float32, device=dev)  # (energy + 1)^(1/8), aq_mode 2 / 3
         self.qp_flags = torch.zeros((B, nmb), dtype=u8, device=dev)       # MB carries mb_qp_delta
         self.qp_pre = torch.zeros((B, nmb), dtype=u8, device=dev)         # ... as encode_inter saw it (0 / 1; 2: intra)
         self.intra_count = torch.zeros((B,), dtype=i32, device=dev)
@@ -656,20 +675,29 @@ class GpuH264Encoder:
         """Pad each slot's display picture of this coding step (``disp``: [B] display indices,
         ``disp_d`` the same on the device): one launch, per-slot frame selection.  With the
         step's tables ``st`` and variance AQ on, the same launch writes the AQ offsets
-        (``st["aq_done"]``) where the kernel library has it and takes the shapes."""
+        (``st["aq_done"]``) where the kernel library has it and takes the shapes -- with
+        auto-variance AQ the terms of its finish launch (``st["aq_terms_done"]``)."""
         B, F, h, w = y.shape
         cs = u.shape[2] * u.shape[3]
         same = bool((disp == disp[0]).all())
         with self.stage_timer("prep"):
             if st is not None:
-                st["aq_done"] = False
-                if self.p.aq_strength > 0 and hasattr(self.hip, "prep_aq"):
+                st["aq_done"] = st["aq_terms_done"] = False
+                if self.aq_auto:
+                    t = int(disp[0]) if same else 0
+                    st["aq_terms_done"] = self.hip.prep_aq_terms(
+                        y[:, t].data_ptr(), u[:, t].data_ptr(), v[:, t].data_ptr(), w, h, F * h * w, F * cs, B,
+                        self._ptr(self.src[0]), self._ptr(self.src[1]), self._ptr(self.src[2]), self.W, self.H,
+                        self._ptr(self.aq_terms), self._stream(), 0 if same else disp_d.data_ptr())
+                    if st["aq_terms_done"]:
+                        return
+                elif self.aq_strength > 0 and hasattr(self.hip, "prep_aq"):
                     t = int(disp[0]) if same else 0
                     extra, stride = self._mbtree_rows()
                     st["aq_done"] = self.hip.prep_aq(
                         y[:, t].data_ptr(), u[:, t].data_ptr(), v[:, t].data_ptr(), w, h, F * h * w, F * cs, B,
                         self._ptr(self.src[0]), self._ptr(self.src[1]), self._ptr(self.src[2]), self.W, self.H,
-                        float(self.p.aq_strength), self._ptr(self.aq), self._stream(),
+                        self.aq_strength, self._ptr(self.aq), self._stream(),
                         0 if same else disp_d.data_ptr(), extra, stride, st["route"])
                     if st["aq_done"]:
                         return
@@ -710,12 +738,21 @@ class GpuH264Encoder:
         aq = 0
         mbt = self._mbtree
         stt = self.stage_timer
-        if self.p.aq_strength > 0 or mbt is not None:
+        if self.aq_strength > 0 or mbt is not None:
             aq = P(self.aq)
-            if not st.get("aq_done"):  # (else: written with the padding, _prep_step)
+            if self.aq_auto:
+                # auto-variance: the terms (unless written with the padding, _prep_step), then the
+                # per-slot sums and offsets
                 extra, stride = self._mbtree_rows()
                 with stt("aq"):
-                    self.hip.aq_offsets(B, wmb, hmb, sy, su, sv, float(self.p.aq_strength), aq, s, extra, stride, rt)
+                    if not st.get("aq_terms_done"):
+                        self.hip.aq_terms(B, wmb, hmb, sy, su, sv, P(self.aq_terms), s)
+                    self.hip.aq_auto_finish(B, self.nmb, P(self.aq_terms), self.aq_auto, self.aq_strength, aq, s,
+                                            extra, stride, rt)
+            elif not st.get("aq_done"):  # (else: written with the padding, _prep_step)
+                extra, stride = self._mbtree_rows()
+                with stt("aq"):
+                    self.hip.aq_offsets(B, wmb, hmb, sy, su, sv, self.aq_strength, aq, s, extra, stride, rt)
         cqo = self.p.chroma_qp_offset
         inter = st["P"] or st["B"]
         # encode_inter leaves the mb_qp_delta flag of its MBs for qp_fixup (a kernel library from

@@ -5,7 +5,8 @@ client.go:115) with gfx950 kernels, CABAC included:
 
 per frame step t (frame t of every slot):
   prep (u8/u16 -> padded u16 planes)
-  -> hevc_aq: per-CTB QP (variance AQ + MB-tree offsets, one quantization group per CTB)
+  -> hevc_aq: per-CTB QP (variance AQ + MB-tree offsets, one quantization group per CTB;
+     aq_mode 2 / 3: hevc_aq_terms + hevc_aq_auto_finish, auto-variance over the picture)
   -> I: hevc_intra_analyze (CTB-parallel open-loop CU/mode decision)
         + hevc_intra_recon (CTB wavefront, closed loop)
      P: lookahead motion search + hevc_inter (CU-parallel) + intra CUs (wavefront)
@@ -67,6 +68,17 @@ class HevcParams:
     # into one QP per CTB coded with cu_qp_delta (csrc/kernels/hevc_filters.hip hevc_aq_ctb);
     # 0 disables
     aq_strength: float = 1.0
+    # x265 --aq-mode: 0 off (as aq_strength 0), 1 the rule above, 2 auto-variance (what x265's
+    # -tune ssim selects), 3 auto-variance with a dark-scene bias.  2 / 3 are x264's formulas, as
+    # mode 1 here uses x264's constants: a = (AC energy / 4^(bit_depth - 8) + 1)^(1/8) per 16x16
+    # block, m = mean a and avg = m - 0.5 (mean a^2 - 14) / m over the coded picture, offset =
+    # strength * m * (a - avg) [+ strength * (1 - 14 / a^2) in mode 3]; cutree, the CTB average
+    # and the clamps follow as in mode 1 (hevc_aq_terms, hevc_aq_auto_finish; aq_auto.h).  x265's
+    # own exponent and constant for these modes differ slightly from x264's; they are not
+    # reproduced here.  Content suite BD-rate on PSNR-Y against mode 1: mode 2 +0.44 %, mode 3
+    # +1.54 %; no throughput difference the suite's fps column resolves (1,441 / 1,482 / 1,474 fps);
+    # SSIM not measured for HEVC (profiles/aq_auto_variance.md) -- opt-in
+    aq_mode: int = 1
     # x265 --cutree (default on): lookahead propagation -> per-block QP offsets added before
     # the CTB average (needs the lookahead and its block grid equal to the 16x16 grid)
     cutree: bool = True
@@ -174,8 +186,12 @@ class HevcParams:
     def eff_bframes(self) -> int:
         return 0 if (self.intra_only or self.keyint > 0) else max(0, int(self.bframes))
 
+    def eff_aq_strength(self) -> float:
+        """The variance-AQ strength the kernels get: aq_mode 0 is strength 0."""
+        return float(self.aq_strength) if self.aq_mode else 0.0
+
     def adaptive_qp(self) -> bool:
-        return self.aq_strength > 0 or (self.cutree and self.lookahead and self.crf is not None)
+        return self.eff_aq_strength() > 0 or (self.cutree and self.lookahead and self.crf is not None)
 
     def host_cfg(self) -> dict:
         return dict(width=self.width, height=self.height, bit_depth=self.bit_depth, fps=self.fps,
@@ -244,6 +260,8 @@ class GpuHevcEncoder:
             raise ValueError("width and height must be even")
         if params.bit_depth not in (8, 10):
             raise ValueError("bit_depth must be 8 or 10")
+        if isinstance(params.aq_mode, bool) or params.aq_mode not in (0, 1, 2, 3):
+            raise ValueError("aq_mode must be 0 (off), 1 (variance), 2 (auto-variance) or 3 (auto-variance, biased)")
         self.p = params
         self.B = int(slots)
         d = torch.device(device)
@@ -336,6 +354,12 @@ class GpuHevcEncoder:
         self.qp = torch.zeros((B,), dtype=torch.int32, device=dev)
         self.ctb_qp = torch.zeros((B, self.nctb), dtype=torch.int32, device=dev)  # QpY per CTB
         self.mb_aq = torch.zeros((B, nmb), dtype=torch.int8, device=dev)           # ME lambda offsets
+        # auto-variance AQ shapes the variance part only: with strength 0 (cutree alone) hevc_aq runs
+        self.aq_auto = int(params.aq_mode) if (params.aq_mode in (2, 3) and params.eff_aq_strength() > 0) else 0
+        if self.aq_auto:
+            if not hasattr(self.hip, "hevc_aq_auto_finish"):
+                raise RuntimeError("aq_mode 2 / 3 need a kernel library with the auto-variance AQ kernels (rebuild)")
+            self.aq_terms = torch.zeros((B, nmb), dtype=torch.float32, device=dev)  # (energy + 1)^(1/8) per 16x16 block
         self._cutree = None  # [B, F, nmb] float MB-tree offsets of the batch being encoded
         self.run = torch.zeros((B,), dtype=torch.int8, device=dev)
         self.err = torch.zeros((1,), dtype=torch.int32, device=dev)
@@ -881,9 +905,15 @@ class GpuHevcEncoder:
                 ct = self._cutree
                 extra, estride, erows = ct.data_ptr() + d * ct.shape[2] * 4, ct.shape[1] * ct.shape[2], self._cutree_rows
             with st("aq"):
-                self.hip.hevc_aq(B, self.W, self.H, bd, p(self.src[0]), p(self.src[1]), p(self.src[2]), p(self.qp),
-                                 float(self.p.aq_strength) if self.p.adaptive_qp() else 0.0, extra, estride, erows,
-                                 p(self.ctb_qp), p(self.mb_aq), s)
+                if self.aq_auto:
+                    self.hip.hevc_aq_terms(B, self.W, self.H, bd, p(self.src[0]), p(self.src[1]), p(self.src[2]),
+                                           p(self.aq_terms), s)
+                    self.hip.hevc_aq_auto_finish(B, self.W, self.H, p(self.aq_terms), p(self.qp), self.aq_auto,
+                                                 self.p.eff_aq_strength(), extra, estride, erows, p(self.ctb_qp),
+                                                 p(self.mb_aq), s)
+                else:
+                    self.hip.hevc_aq(B, self.W, self.H, bd, p(self.src[0]), p(self.src[1]), p(self.src[2]), p(self.qp),
+                                     self.p.eff_aq_strength(), extra, estride, erows, p(self.ctb_qp), p(self.mb_aq), s)
             ci, r0, r1 = pic.slot, pic.s0, pic.s1
             cur, ref = self.rec[ci], self.rec[r0]
             kb = t % 2

@@ -59,6 +59,7 @@ H264 = {
     "MIVC_REF_RANGE": "ref_range",
     "MIVC_REF_GATE": "ref_gate",
     "MIVC_SLICES": "slices",
+    "MIVC_AQ_MODE": "aq_mode",
 }
 # env name -> HevcParams field
 HEVC = {
@@ -73,6 +74,7 @@ HEVC = {
     "MIVC_HEVC_INTER8_OVERHEAD": "inter8_overhead",
     "MIVC_HEVC_TU_INTER_DEPTH": "tu_inter_depth",
     "MIVC_HEVC_SDH": "sdh",
+    "MIVC_HEVC_AQ_MODE": "aq_mode",
 }
 # bench.py shape knobs (they change what is measured, so they also need --allow-knobs)
 # (MIVC_HIP_LIB: an alternative kernel library, tools/build_variant.py -- same-box A/B timing)

@@ -88,6 +88,10 @@ CONFIGS = {
     "tdir_pyramid": dict(direct="temporal", pyramid=True),
     "i4p": dict(i4x4_in_p=True),  # x264's analysis: Intra4x4 trials in P / B pictures too
     "default": dict(),  # the current defaults
+    # x264 --aq-mode 2 / 3 (auto-variance, with the dark-scene bias) against the default's mode 1:
+    # run with --configs default,aq2,aq3
+    "aq2": dict(aq_mode=2),
+    "aq3": dict(aq_mode=3),
 }
 # HEVC (GpuHevcEncoder) configurations: x265 --signhide, --bframes variants
 HEVC_CONFIGS = {
@@ -119,6 +123,9 @@ HEVC_CONFIGS = {
     # x265 medium's --tu-inter-depth 1 and --signhide, re-measured on the round-6 encoder
     "tud1": dict(tu_inter_depth=1),
     "sdh": dict(sdh=True),
+    # x265 --aq-mode 2 / 3 (auto-variance AQ; 2 is what -tune ssim selects)
+    "aq2": dict(aq_mode=2),
+    "aq3": dict(aq_mode=3),
 }
 
 
@@ -196,6 +203,22 @@ def table(args):
         for c in configs[1:]:
             tst = [(p["crf"], p["kbps"], p["psnr"]) for p in pts if p["kind"] == k and p["config"] == c]
             v = bd_rate(ref, tst)
+            allv[c].append(v)
+            row.append(f"{v:+.2f} %")
+        print(f"| {k} | " + " | ".join(row) + " |")
+    print("| **mean** | " + " | ".join(f"{np.mean(allv[c]):+.2f} %" for c in configs[1:]) + " |")
+    if not all(0.0 < p.get("ssim", 0.0) < 1.0 for p in pts):
+        return
+    # the same on SSIM-Y, as -10 log10(1 - SSIM) so that the curves are as straight as PSNR's
+    sdb = lambda p: -10.0 * float(np.log10(1.0 - p["ssim"]))  # noqa: E731
+    print(f"\n| class | " + " | ".join(f"{c} vs {base} (BD-rate, SSIM-Y)" for c in configs[1:]) + " |")
+    print("|---|" + "---|" * (len(configs) - 1))
+    allv = {c: [] for c in configs[1:]}
+    for k in kinds:
+        ref = [(p["crf"], p["kbps"], sdb(p)) for p in pts if p["kind"] == k and p["config"] == base]
+        row = []
+        for c in configs[1:]:
+            v = bd_rate(ref, [(p["crf"], p["kbps"], sdb(p)) for p in pts if p["kind"] == k and p["config"] == c])
             allv[c].append(v)
             row.append(f"{v:+.2f} %")
         print(f"| {k} | " + " | ".join(row) + " |")
