@@ -1187,12 +1187,15 @@ MIVC_HD size_t cabac_write_slice_data(const CabacSliceInfo& si, CabacNb* nb, uin
 // The same slice data through the GPU decomposition: every MB binarised on its own into
 // symbols (any order), then the symbols arithmetic-coded in MB order.  Must produce the
 // bytes of cabac_write_slice_data (a CPU test pins it).  syms: scratch >= total symbols.
+// masks (nullable, one per MB of the picture): the block masks, as the GPU path gets them from
+// the inter kernels -- the levels of a block whose bit is clear are then never read.
 inline size_t cabac_write_slice_data_symbols(const CabacSliceInfo& si, CabacNb* nb, uint8_t* states, CabacBuf* out,
                                              const MbHeader* hdr, const int16_t* coef, int n, uint16_t* syms,
-                                             size_t cap_syms, int* nsyms_out) {
+                                             size_t cap_syms, int* nsyms_out, const uint32_t* masks = nullptr) {
   const int end = si.first_mb + n;
   for (int a = end - 1; a >= si.first_mb; --a)  // reverse order: nothing depends on coding order
-    cabac_prepare_mb(si, hdr, a, cabac_block_mask(hdr[a], coef + static_cast<size_t>(a) * kCoefPerMb), nb[a]);
+    cabac_prepare_mb(si, hdr, a,
+                     masks ? masks[a] : cabac_block_mask(hdr[a], coef + static_cast<size_t>(a) * kCoefPerMb), nb[a]);
   cabac_qp_chain(si, nb, n);
   size_t total = 0;
   for (int a = si.first_mb; a < end; ++a) {

@@ -45,6 +45,12 @@ enum : int {
   COEF_CHROMA_AC = 280,   // 2 x 4 blocks x 16 (index 0 unused)
   kCoefPerMb = 408,
 };
+// Records are dense: every level is written, zeros included.  For the GPU CABAC path the GPU
+// inter kernels also leave every MB's non-zero block mask (cabac_block_mask's layout,
+// h264_cabac.h) beside the record (encode_inter's mask_pre), so that nobody reads 816 bytes back
+// to learn which blocks are zero.  kBlockMaskIntra in place of a mask: the MB was handed to the
+// intra kernels, which decide its levels later; its mask comes from the levels.
+constexpr uint32_t kBlockMaskIntra = 0x80000000u;
 
 enum : uint8_t {
   MBF_SKIP = 1,     // encoder proposes P_Skip / B_Skip

@@ -12,6 +12,7 @@
 
 #include "../common/h264_enc_math.h"
 #include "annexb.h"
+#include "../common/h264_cabac.h"
 #include "cabac_writer.h"
 #include "cavlc_writer.h"
 #include "cpu_encoder.h"
@@ -719,6 +720,34 @@ PYBIND11_MODULE(_host, m) {
     int nsyms = 0;
     std::vector<uint8_t> b = cabac_slice_data_symbols(sps, pps, sh, mh, coef.data(), nmb, &nsyms);
     return py::make_tuple(to_bytes(a), to_bytes(b), nsyms);
+  });
+  // every record's non-zero block mask (cabac_block_mask), uint32 [nmb]
+  m.def("cabac_block_masks", [](py::array_t<uint8_t, py::array::c_style> hdr, py::array_t<int16_t, py::array::c_style> coef) {
+    const py::ssize_t nmb = hdr.size() / static_cast<py::ssize_t>(sizeof(MbHeader));
+    if (hdr.size() != nmb * static_cast<py::ssize_t>(sizeof(MbHeader)) || coef.size() != nmb * kCoefPerMb)
+      throw std::runtime_error("header / coef arrays have wrong sizes");
+    const MbHeader* mh = reinterpret_cast<const MbHeader*>(hdr.data());
+    py::array_t<uint32_t> out(nmb);
+    for (py::ssize_t a = 0; a < nmb; ++a) out.mutable_at(a) = cabac_block_mask(mh[a], coef.data() + a * kCoefPerMb);
+    return out;
+  });
+  // the symbol path with the block masks handed in (as the GPU path gets them from the inter
+  // kernels): blocks whose bit is clear are never read
+  m.def("cabac_slice_data_masks", [](const py::dict& cfg, const py::dict& fp, py::array_t<uint8_t, py::array::c_style> hdr,
+                                      py::array_t<int16_t, py::array::c_style> coef,
+                                      py::array_t<uint32_t, py::array::c_style> masks) {
+    EncoderConfig c = cfg_from(cfg);
+    c.cabac = 1;
+    SPS sps = make_sps(c);
+    PPS pps = make_pps(c);
+    int nmb = sps.width_mbs * sps.height_mbs;
+    if (hdr.size() != static_cast<py::ssize_t>(nmb * sizeof(MbHeader))) throw std::runtime_error("header array has wrong size");
+    if (coef.size() != static_cast<py::ssize_t>(nmb) * kCoefPerMb) throw std::runtime_error("coef array has wrong size");
+    if (masks.size() != nmb) throw std::runtime_error("mask array has wrong size");
+    SliceHeader sh = slice_header_from(c, sps, pps, fp);
+    int nsyms = 0;
+    return to_bytes(cabac_slice_data_symbols(sps, pps, sh, reinterpret_cast<const MbHeader*>(hdr.data()), coef.data(), nmb,
+                                             &nsyms, masks.data()));
   });
 
   m.def(

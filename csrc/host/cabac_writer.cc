@@ -55,7 +55,7 @@ std::vector<uint8_t> cabac_slice_data(const SPS& sps, const PPS& pps, const Slic
 }
 
 std::vector<uint8_t> cabac_slice_data_symbols(const SPS& sps, const PPS& pps, const SliceHeader& sh, const MbHeader* mbs,
-                                              const int16_t* coef, int num_mbs, int* nsyms) {
+                                              const int16_t* coef, int num_mbs, int* nsyms, const uint32_t* masks) {
   const int nmb = sps.width_mbs * sps.height_mbs;
   CabacSliceInfo si{};
   si.slice_type = sh.slice_type;
@@ -71,7 +71,8 @@ std::vector<uint8_t> cabac_slice_data_symbols(const SPS& sps, const PPS& pps, co
   std::vector<uint8_t> out(static_cast<size_t>(num_mbs) * 4000 + 4096);
   uint8_t states[kCabacContexts];
   CabacBuf buf{out.data(), out.size(), 0, 0};
-  cabac_write_slice_data_symbols(si, nb.data(), states, &buf, mbs, coef, num_mbs, syms.data(), syms.size(), nsyms);
+  cabac_write_slice_data_symbols(si, nb.data(), states, &buf, mbs, coef, num_mbs, syms.data(), syms.size(), nsyms,
+                                 masks);
   if (buf.overflow) throw std::runtime_error("CABAC symbol path overflow");
   out.resize(buf.n);
   return out;

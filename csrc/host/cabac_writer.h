@@ -23,9 +23,11 @@ std::vector<uint8_t> cabac_slice_data(const SPS& sps, const PPS& pps, const Slic
                                       const int16_t* coef, int num_mbs, SliceStats* stats = nullptr);
 
 // Slice data through the symbol path (per-MB binarisation, then arithmetic coding): the
-// decomposition the GPU uses.  Returns the bytes and the symbol count.
+// decomposition the GPU uses.  Returns the bytes and the symbol count.  masks (nullable, one per
+// MB of the picture): precomputed block masks instead of cabac_block_mask of the levels.
 std::vector<uint8_t> cabac_slice_data_symbols(const SPS& sps, const PPS& pps, const SliceHeader& sh, const MbHeader* mbs,
-                                              const int16_t* coef, int num_mbs, int* nsyms);
+                                              const int16_t* coef, int num_mbs, int* nsyms,
+                                              const uint32_t* masks = nullptr);
 
 }  // namespace h264
 }  // namespace mivc

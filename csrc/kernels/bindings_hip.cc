@@ -93,7 +93,7 @@ void mivc_launch_encode_inter(int B, int wmb, int hmb, const uint8_t* src_y, con
                               int bmode, int t8, const int16_t* mv8, void* stream, const int* w1, int nref,
                               const uint8_t* const* xref_u, const uint8_t* const* xref_v, const int8_t* mref,
                               const int* wp, int trellis, float trellis_lambda, const void* route, int nbuf,
-                              uint8_t* qp_flags);
+                              uint8_t* qp_flags, uint32_t* mask_pre);
 void mivc_launch_wp_stats16(const uint16_t* y, const uint16_t* u, const uint16_t* v, int w, int h, int npics,
                             unsigned long long* out, void* stream);
 void mivc_launch_wp_stats(const uint8_t* y, const uint8_t* u, const uint8_t* v, int w, int h, int npics,
@@ -178,7 +178,7 @@ void mivc_launch_cabac_bin(int B, int wmb, int hmb, const void* hdr, const int16
                            int* cnt, long long* off, int* tot, uint16_t* pool, long long pool_cap,
                            long long* pool_used, long long* base, int* total, const int* slot_qp, int slice_type,
                            int num_ref_l0, int num_ref_l1, int t8x8_mode, int* err, void* stream, const void* route,
-                           int slice_rows);
+                           int slice_rows, const uint32_t* pre);
 void mivc_launch_cabac_code(int L, int B, uint16_t* pool, const long long* base, const int* total,
                             const uint32_t* hdr_bits, const int* hdr_nbits, const int* slot_qp,
                             unsigned long long itypes, int* bytes, uint8_t* out, long long* out_off, int* err,
@@ -217,6 +217,9 @@ void* S(uintptr_t s) { return reinterpret_cast<void*>(s); }
 PYBIND11_MODULE(_hip, m) {
   m.doc() = "govideocompressor_amd gfx950 kernels (raw-pointer launch shims)";
   m.attr("arch") = "gfx950";
+  // a feature a caller tests for before it passes its arguments (an older library lacks them):
+  // encode_inter's mask_pre with cabac_bin's pre
+  m.attr("inter_block_mask") = true;
   // sizeof(SlotRoute): the row size the routed kernels step by (ROUTE_DTYPE in models/h264_gpu.py)
   m.def("route_bytes", []() { return static_cast<int>(sizeof(mivc::gpu::SlotRoute)); });
 
@@ -448,7 +451,9 @@ PYBIND11_MODULE(_hip, m) {
            uintptr_t intra_flag, uintptr_t intra_count, uintptr_t stream, uintptr_t aq, uintptr_t ref1_u,
            uintptr_t ref1_v, int bmode, int t8, uintptr_t mv8, std::vector<int> w1, std::vector<uintptr_t> xref_u,
            std::vector<uintptr_t> xref_v, uintptr_t mref, uintptr_t wp, int trellis, float trellis_lambda,
-           uintptr_t route, int nbuf, uintptr_t qp_flags) {
+           uintptr_t route, int nbuf, uintptr_t qp_flags, uintptr_t mask_pre) {
+          // mask_pre: uint32 [B, nmb], every coded MB's CABAC block mask (cabac_bin's pre)
+          if (mask_pre & 3) throw std::invalid_argument("encode_inter: mask_pre must be 4-byte aligned");
           // xref_u / xref_v: chroma of RefPicList0[1..]; w1: implicit list-1 weight per list-0 picture
           if (bmode && (!ref1_u || !ref1_v)) throw std::invalid_argument("encode_inter: B mode needs the list-1 chroma");
           const size_t n = xref_u.size() + 1;
@@ -471,7 +476,7 @@ PYBIND11_MODULE(_hip, m) {
                                    P<int>(intra_count), P<int8_t>(aq), P<uint8_t>(ref1_u), P<uint8_t>(ref1_v), bmode,
                                    t8, P<int16_t>(mv8), S(stream), w.data(), static_cast<int>(n), xu, xv,
                                    bmode ? nullptr : P<int8_t>(mref), P<int>(wp), trellis, trellis_lambda, P<void>(route),
-                                   nbuf, P<uint8_t>(qp_flags));
+                                   nbuf, P<uint8_t>(qp_flags), P<uint32_t>(mask_pre));
         }, py::arg("B"), py::arg("wmb"), py::arg("hmb"), py::arg("sy"), py::arg("su"), py::arg("sv"), py::arg("fy"),
         py::arg("fu"), py::arg("fv"), py::arg("ry"), py::arg("ru"), py::arg("rv"), py::arg("pred"), py::arg("mv"),
         py::arg("me_cost"), py::arg("intra_cost"), py::arg("qp"), py::arg("cqo"), py::arg("hdr"), py::arg("coef"),
@@ -479,7 +484,8 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("ref1_u") = 0, py::arg("ref1_v") = 0, py::arg("bmode") = 0, py::arg("t8") = 0, py::arg("mv8") = 0,
         py::arg("w1") = std::vector<int>{32}, py::arg("xref_u") = std::vector<uintptr_t>{},
         py::arg("xref_v") = std::vector<uintptr_t>{}, py::arg("mref") = 0, py::arg("wp") = 0, py::arg("trellis") = 0,
-        py::arg("trellis_lambda") = 1.0f, py::arg("route") = 0, py::arg("nbuf") = 0, py::arg("qp_flags") = 0);
+        py::arg("trellis_lambda") = 1.0f, py::arg("route") = 0, py::arg("nbuf") = 0, py::arg("qp_flags") = 0,
+        py::arg("mask_pre") = 0);
   m.def("wp_stats16", [](uintptr_t y, uintptr_t u, uintptr_t v, int w, int h, int npics, uintptr_t out, uintptr_t stream) {
     if (w % 2 || h % 2 || npics <= 0) throw std::invalid_argument("wp_stats16: even picture sizes, npics > 0");
     mivc_launch_wp_stats16(P<uint16_t>(y), P<uint16_t>(u), P<uint16_t>(v), w, h, npics, P<unsigned long long>(out),
@@ -834,18 +840,21 @@ PYBIND11_MODULE(_hip, m) {
                         uintptr_t cnt, uintptr_t off, uintptr_t tot, uintptr_t pool, long long pool_cap,
                         uintptr_t pool_used, uintptr_t base, uintptr_t total, uintptr_t slot_qp, int slice_type,
                         int num_ref_l0, int num_ref_l1, int t8x8_mode, uintptr_t err, uintptr_t stream, uintptr_t route,
-                        int slice_rows) {
+                        int slice_rows, uintptr_t pre) {
+    // pre (needs route): encode_inter's mask_pre of this step; MBs of slots coding a P / B
+    // picture take their mask from it, and their levels are not read
+    if (pre && !route) throw std::invalid_argument("cabac_bin: pre needs the step's route");
     if ((pool & 15) != 0) throw std::invalid_argument("cabac_bin: symbol pool must be 16-byte aligned");
     if (B < 1 || wmb < 1 || hmb < 1) throw std::invalid_argument("cabac_bin: bad geometry");
     mivc_launch_cabac_bin(B, wmb, hmb, P<void>(hdr), P<int16_t>(coef), P<uint32_t>(mask), P<void>(nb), P<int>(cnt),
                           P<long long>(off), P<int>(tot), P<uint16_t>(pool), pool_cap, P<long long>(pool_used),
                           P<long long>(base), P<int>(total), P<int>(slot_qp), slice_type, num_ref_l0, num_ref_l1,
-                          t8x8_mode, P<int>(err), S(stream), P<void>(route), slice_rows);
+                          t8x8_mode, P<int>(err), S(stream), P<void>(route), slice_rows, P<uint32_t>(pre));
   }, py::arg("B"), py::arg("wmb"), py::arg("hmb"), py::arg("hdr"), py::arg("coef"), py::arg("mask"), py::arg("nb"),
      py::arg("cnt"), py::arg("off"), py::arg("tot"), py::arg("pool"), py::arg("pool_cap"), py::arg("pool_used"),
      py::arg("base"), py::arg("total"), py::arg("slot_qp"), py::arg("slice_type"), py::arg("num_ref_l0"),
      py::arg("num_ref_l1"), py::arg("t8x8_mode"), py::arg("err"), py::arg("stream"), py::arg("route") = 0,
-     py::arg("slice_rows") = 0);
+     py::arg("slice_rows") = 0, py::arg("pre") = 0);
   m.def("cabac_code", [](int L, int B, uintptr_t pool, uintptr_t base, uintptr_t total, uintptr_t hdr_bits,
                          uintptr_t hdr_nbits, uintptr_t slot_qp, unsigned long long itypes, uintptr_t bytes,
                          uintptr_t out, uintptr_t out_off, uintptr_t err, uintptr_t stream, uintptr_t host_out,

@@ -10,7 +10,10 @@
 //
 // Two launches:
 //   mivc_launch_cabac_bin   one frame step (B slots, S slices each), into a symbol pool
-//     cabac_mask    (nmb/2 x B, wave64)    non-zero mask of every 4x4 / DC block
+//     cabac_mask    (nmb/32 x B, wave64)   non-zero mask of every 4x4 / DC block: the word the
+//                                          inter kernels left for an MB they coded (`pre`,
+//                                          encode_inter's mask_pre), else from the MB's levels
+//                                          (I pictures, MBs handed to the intra kernels)
 //     cabac_prep    (nmb/64 x B, 64)       lane per MB: coding state (skip, cbp, mvd, cbf ...)
 //     cabac_chain   (B, 64)                mb_qp_delta chain (QP_pred scan) per slot
 //     cabac_count   (nmb/64 x B, 64)       lane per MB: symbol count
@@ -68,7 +71,12 @@ struct CabacBinArgs {
   // MB rows; the last one may be shorter).  Slice index ls = slot * per_slot + mb / slice_mbs
   // addresses tot / base / total; symbol offsets are relative to the slice.
   int slice_mbs, per_slot;
+  // [B, nmb] (nullable; needs rt): the block masks the inter kernels left (encode_inter's
+  // mask_pre) -- the word of an MB of a slot coding a P or B picture this step is its mask,
+  // unless it is kBlockMaskIntra (the MB went to the intra kernels: its levels say)
+  const uint32_t* pre;
 };
+
 
 __device__ __forceinline__ int slice_first(const CabacBinArgs& a, int mb) { return (mb / a.slice_mbs) * a.slice_mbs; }
 __device__ __forceinline__ int slice_end(const CabacBinArgs& a, int mb) {
@@ -98,16 +106,28 @@ constexpr int kMaskSpan = 16;
 __global__ __launch_bounds__(64) void cabac_mask(CabacBinArgs a) {
   const Geom& g = a.g;
   const int lane = threadIdx.x, sub = lane & 31;
-  const int slot = blockIdx.y;
+  const int slot = blockIdx.y, nmb = g.nmb();
+  // The workgroup's 2 * kMaskSpan MBs, one per lane 0-31.  Where the slot codes a P or B picture
+  // this step (another slot's words are of an earlier step), the inter kernels' word of an MB is
+  // its mask and leaves at once; the levels of such an MB are never loaded.  `need`: the MBs whose mask the levels say -- all of them without `pre`.
+  const bool routed = a.pre && a.rt && (a.rt[slot].kind == SK_P || a.rt[slot].kind == SK_B);  // (uniform)
+  const int mb_l = blockIdx.x * (2 * kMaskSpan) + lane;
+  const bool mine = lane < 2 * kMaskSpan && mb_l < nmb;
+  const size_t o_l = static_cast<size_t>(slot) * nmb + (mine ? mb_l : 0);
+  const uint32_t pw = (routed && mine) ? a.pre[o_l] : h264::kBlockMaskIntra;
+  if (mine && pw != h264::kBlockMaskIntra) a.mask[o_l] = pw;
+  const unsigned long long need = __ballot(mine && pw == h264::kBlockMaskIntra);
   for (int it = 0; it < kMaskSpan; ++it) {
+  if (((need >> (2 * it)) & 3ull) == 0) continue;  // (uniform) neither MB of this step reads levels
   const int mb = (blockIdx.x * kMaskSpan + it) * 2 + (lane >> 5);
-  if ((blockIdx.x * kMaskSpan + it) * 2 >= g.nmb()) break;  // (uniform)
-  const bool live = mb < g.nmb();
-  const size_t o = static_cast<size_t>(slot) * g.nmb() + (live ? mb : 0);
+  const bool rd = (need >> (2 * it + (lane >> 5))) & 1ull;  // per half-wave (only live MBs): loads are predicated, the ballot is not
+  const size_t o = static_cast<size_t>(slot) * nmb + (rd ? mb : 0);
   const int16_t* c = a.coef + o * h264::kCoefPerMb;
-  const bool i16 = a.hdr[o].kind == h264::MBK_I16x16;
+  const bool i16 = rd && a.hdr[o].kind == h264::MBK_I16x16;
   bool nz = false;
-  if (sub < 16 || (sub >= 19 && sub < 27)) {
+  if (!rd) {
+    // nothing to load
+  } else if (sub < 16 || (sub >= 19 && sub < 27)) {
     const int16_t* p = sub < 16 ? c + h264::COEF_LUMA + sub * 16 : c + h264::COEF_CHROMA_AC + (sub - 19) * 16;
     const uint4 q0 = reinterpret_cast<const uint4*>(p)[0];
     const uint4 q1 = reinterpret_cast<const uint4*>(p)[1];
@@ -123,7 +143,7 @@ __global__ __launch_bounds__(64) void cabac_mask(CabacBinArgs a) {
   }
   const unsigned long long bal = __ballot(nz);
   const uint32_t m = static_cast<uint32_t>((bal >> (lane & 32)) & 0x7FFFFFFull);
-  if (live && sub == 0) a.mask[o] = m;
+  if (rd && sub == 0) a.mask[o] = m;
   }
 }
 
@@ -570,8 +590,10 @@ extern "C" void mivc_launch_cabac_bin(int B, int wmb, int hmb, const void* hdr, 
                                       void* nb, int* cnt, long long* off, int* tot, uint16_t* pool,
                                       long long pool_cap, long long* pool_used, long long* base, int* total,
                                       const int* slot_qp, int slice_type, int num_ref_l0, int num_ref_l1,
-                                      int t8x8_mode, int* err, void* stream, const void* route, int slice_rows) {
+                                      int t8x8_mode, int* err, void* stream, const void* route, int slice_rows,
+                                      const uint32_t* pre) {
   CabacBinArgs a;
+  a.pre = route ? pre : nullptr;
   const int rows = (slice_rows > 0 && slice_rows < hmb) ? slice_rows : hmb;
   a.slice_mbs = rows * wmb;
   a.per_slot = (hmb + rows - 1) / rows;

@@ -65,6 +65,11 @@ struct InterArgs {
   // mb_qp_delta), 0 = none, 2 = handed to the intra kernels -- what h264_qp_flags would
   // otherwise read back from the levels (aq.hip)
   uint8_t* qp_flags;
+  // [B, nmb] (nullable): the CABAC non-zero block mask of every MB coded here, in
+  // cabac_block_mask's layout (h264_cabac.h) -- encode_inter_mb writes the luma bits (or
+  // h264::kBlockMaskIntra for an MB it hands to the intra kernels), encode_inter_chroma, next on the
+  // stream, ORs in the chroma bits; cabac_mask then takes the word instead of the levels
+  uint32_t* mask_pre;
 };
 
 // trellis_lite4x4 / trellis_lite8_chunk: h264_trellis.h
@@ -449,14 +454,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
     }
 
     // ---- final levels, dequantisation, inverse transform: res = this block's residual
-    bool any = false;
+    bool any = false;  // this block's residual is added to the prediction
+    bool lnz = false;  // the 16 levels this lane stores (4x4 block / chunk of an 8x8 block) have a non-zero one
     if (use8_wave) {  // wave-uniform
       // 8x8: levels in 8x8 scan order (chunk k of the quad's block), dequantised into the
       // transform buffer, inverse 8x8 (lanes on rows / columns 2k, 2k + 1), then every lane
       // takes its 4x4 part of the residual
       if (use8) {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) lv[i] = keep8 ? lv[i] : 0;
+        for (int i = 0; i < 16; ++i) {
+          lv[i] = keep8 ? lv[i] : 0;
+          lnz |= lv[i] != 0;
+        }
         store_levels(coef + h264::COEF_LUMA + l * 16, lv);
         const int m = qp % 6, q6 = qp / 6;
 #pragma unroll
@@ -493,6 +502,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
         sv[i] = keep4 ? lv[h264::kZigzag4x4[i]] : 0;
         any |= sv[i] != 0;
       }
+      lnz = any;
       store_levels(coef + h264::COEF_LUMA + l * 16, sv);
       int dv[3];
 #pragma unroll
@@ -507,6 +517,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
       // next on the stream, raises it to 1 for an MB that has chroma levels only
       const uint64_t luma_any = __ballot(any);
       if (live && l == 0) a.qp_flags[o] = !work ? 2 : (((luma_any >> (16 * q)) & 0xFFFFu) != 0 ? 1 : 0);
+    }
+    if (a.mask_pre) {
+      // bit l = this lane's 16 stored levels (`lnz` is false outside `work`); the ballot is
+      // formed by every lane before the row's lane 0 is picked
+      const uint64_t luma_nz = __ballot(lnz);
+      if (live && l == 0) a.mask_pre[o] = work ? static_cast<uint32_t>((luma_nz >> (16 * q)) & 0xFFFFu) : h264::kBlockMaskIntra;
     }
     if (work) {
       uint8_t* recy = a.rec_y + rcur * g.ysize() + static_cast<size_t>(Y0 + lby) * W + X0 + lbx;
@@ -680,6 +696,7 @@ __global__ __launch_bounds__(64) void encode_inter_chroma(InterArgs a) {
   const int score_c = sum4(score);
   const bool keep_ac = score_c >= 7;
   bool any_c = false;  // this block has an AC level or its component a DC level
+  bool any_ac = false, any_dc = false;  // ... each on its own (any_dc: the same on the quad's four lanes)
   if (work) {
     // chroma DC: 2x2 Hadamard + quantisation with qbits+1 (every lane of the quad: no hand-off)
     const int f[4] = {d0 + d1 + d2 + d3, d0 - d1 + d2 - d3, d0 + d1 - d2 - d3, d0 - d1 - d2 + d3};
@@ -687,12 +704,12 @@ __global__ __launch_bounds__(64) void encode_inter_chroma(InterArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) cl[i] = h264::quant_coef(f[i], mfc[0], 15 + qpc / 6 + 1, 11);
     int sv[16];
-    bool any_ac = false;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       sv[i] = (keep_ac && i > 0) ? lv[h264::kZigzag4x4[i]] : 0;
       any_ac |= sv[i] != 0;
     }
+    any_dc = (cl[0] | cl[1] | cl[2] | cl[3]) != 0;
     store_levels(coef + h264::COEF_CHROMA_AC + (comp * 4 + cb) * 16, sv);
     if (cb == 0) {
       // chroma DC levels (Cb then Cr, 4 x int16 each at COEF_CHROMA_DC)
@@ -706,7 +723,7 @@ __global__ __launch_bounds__(64) void encode_inter_chroma(InterArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) res[r] = (keep_ac && r > 0) ? (lv[r] * dvc[h264::kPosClass[r]]) << (qpc / 6) : 0;
     res[0] = ((fcb * ls) << (qpc / 6)) >> 5;
-    const bool any = any_ac || c0 || c1 || c2 || c3;
+    const bool any = any_ac || any_dc;
     any_c = any;
     if (any) h264::inverse_core4x4(res);
     uint8_t* recc = (comp == 0 ? a.rec_u : a.rec_v) + rcur * g.csize() + static_cast<size_t>(my * 8 + cby) * cw + mx * 8 + cbx;
@@ -723,6 +740,14 @@ __global__ __launch_bounds__(64) void encode_inter_chroma(InterArgs a) {
     // encode_inter_mb wrote the MB's byte from luma; an MB coded here with a chroma level has 1
     const uint64_t chroma_any = __ballot(any_c);
     if (work && (lane & 7) == 0 && ((chroma_any >> (8 * m)) & 0xFFu) != 0) a.qp_flags[o] = 1;
+  }
+  if (a.mask_pre) {
+    // lane & 7 = comp * 4 + cb is the AC bit's index; the DC bits come from the components' first
+    // lanes.  Both ballots by every lane; an MB handed to the intra kernels keeps its h264::kBlockMaskIntra.
+    const uint64_t ac_nz = __ballot(any_ac), dc_nz = __ballot(any_dc);
+    const uint32_t ac = static_cast<uint32_t>((ac_nz >> (8 * m)) & 0xFFu), dcb = static_cast<uint32_t>((dc_nz >> (8 * m)) & 0xFFu);
+    const uint32_t bits = (ac << 19) | ((dcb & 1u) << 17) | (((dcb >> 4) & 1u) << 18);
+    if (work && (lane & 7) == 0 && bits) a.mask_pre[o] |= bits;
   }
 }
 
@@ -741,9 +766,10 @@ extern "C" void mivc_launch_encode_inter(int B, int wmb, int hmb, const uint8_t*
                                          int t8, const int16_t* mv8, void* stream, const int* w1, int nref,
                                          const uint8_t* const* xref_u, const uint8_t* const* xref_v,
                                          const int8_t* mref, const int* wp, int trellis, float trellis_lambda,
-                                         const void* route, int nbuf, uint8_t* qp_flags) {
+                                         const void* route, int nbuf, uint8_t* qp_flags, uint32_t* mask_pre) {
   InterArgs a;
   a.qp_flags = qp_flags;
+  a.mask_pre = mask_pre;
   a.rt = static_cast<const SlotRoute*>(route);
   a.nbuf = nbuf;
   a.trellis = trellis;

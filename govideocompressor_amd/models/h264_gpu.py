@@ -527,6 +527,16 @@ class GpuH264Encoder:
             self.aq_terms = torch.zeros((B, nmb), dtype=torch.float32, device=dev)  # (energy + 1)^(1/8), aq_mode 2 / 3
         self.qp_flags = torch.zeros((B, nmb), dtype=u8, device=dev)       # MB carries mb_qp_delta
         self.qp_pre = torch.zeros((B, nmb), dtype=u8, device=dev)         # ... as encode_inter saw it (0 / 1; 2: intra)
+        # GPU CABAC: the inter kernels leave every coded MB's block mask for cabac_mask, which then
+        # does not read the levels back (a ring like hdr / coef: the words cross to the copy
+        # stream); needs a kernel library with the feature.  _use_mask_pre: a switch for tests.
+        self._use_mask_pre = True
+        self.mask_pre = None
+        if entropy == "gpu" and params.cabac and hasattr(self.hip, "inter_block_mask"):
+            self.mask_pre = [torch.zeros((B, nmb), dtype=i32, device=dev) for _ in range(2)]
+        # tests: fill the level buffer with a non-zero pattern before every step's kernels, so a
+        # reader that strays into a block nobody wrote this step cannot see zeros by luck
+        self._poison_levels = False
         self.intra_count = torch.zeros((B,), dtype=i32, device=dev)
         self.qp = torch.zeros((B,), dtype=i32, device=dev)
         # error flags, one buffer per batch in flight (encode_async: the next batch zeroes its own
@@ -720,14 +730,16 @@ class GpuH264Encoder:
         tx = tdiv(16384 + abs(tdiv(td, 2)), td)
         return max(-1024, min(1023, (tb * tx + 32) >> 6)), 0
 
-    def _encode_step(self, st: dict, hdr, coef, cut=None):
+    def _encode_step(self, st: dict, hdr, coef, cut=None, mask_pre=None):
         """One coding step of every slot (csrc/kernels/route.h): each slot codes its own
         picture (``st``: the step's routing and host-side tables, built by _step_tables).  P
         and B pictures of different slots share the step: the P kernels skip the B slots and
         the B kernels the P slots (they write disjoint per-slot rows of the shared buffers);
         the intra, deblocking and half-sample kernels then run over all slots at once.
         cut: optional [B] bool device tensor -- slots whose P picture is a scene cut (every MB
-        intra, as an I picture would be)."""
+        intra, as an I picture would be).
+        mask_pre: optional [B, nmb] int32 device tensor -- the inter kernels leave their MBs'
+        CABAC block masks in it (for cabac_bin's ``pre``)."""
         s = self._stream()
         B, wmb, hmb = self.B, self.wmb, self.hmb
         P = self._ptr
@@ -758,6 +770,11 @@ class GpuH264Encoder:
         # encode_inter leaves the mb_qp_delta flag of its MBs for qp_fixup (a kernel library from
         # before that argument computes them all from the levels, as on I-picture steps)
         pre = {"qp_flags": P(self.qp_pre)} if (aq and inter and hasattr(self.hip, "prep_aq")) else {}
+        ikw = dict(pre)
+        if mask_pre is not None:
+            ikw.update(mask_pre=P(mask_pre))
+        if self._poison_levels:
+            coef.fill_(0x5A5A)
         if inter:
             self.intra_count.zero_()
         seed0 = seed1 = 0
@@ -828,7 +845,7 @@ class GpuH264Encoder:
                                       P(self.nz), P(self.intra_flag), P(self.intra_count), s, aq,
                                       t8=int(self.p.eff_t8x8()), mv8=mv8, mref=P(self.mref), wp=wp,
                                       trellis=int(self.p.trellis), trellis_lambda=float(self.p.trellis_lambda),
-                                      route=rt, nbuf=NB, **pre)
+                                      route=rt, nbuf=NB, **ikw)
         if st["B"]:
             br = self.p.b_me_range
             spatial = self.p.direct == "spatial"
@@ -880,7 +897,7 @@ class GpuH264Encoder:
                                       P(self.cost_b), P(self.intra_cost), P(self.qp), cqo, P(hdr), P(coef),
                                       P(self.nz), P(self.intra_flag), P(self.intra_count), s, aq, pu, pv, 1,
                                       int(self.p.eff_t8x8()), 0, [32], [], [], 0, 0, int(self.p.trellis),
-                                      float(self.p.trellis_lambda), rt, NB, **pre)
+                                      float(self.p.trellis_lambda), rt, NB, **ikw)
         if inter:
             self.p_intra_mbs += self.intra_count.sum()
             flag_ptr, count_ptr = P(self.intra_flag), P(self.intra_count)
@@ -1163,12 +1180,13 @@ class GpuH264Encoder:
         return out
 
     def _gpu_cabac_bin(self, k: int, g: int, j: int, t: int, pics: list[PicPlan], qps_t, idr_ids: list[int],
-                       qp_dev: torch.Tensor, route: int):
+                       qp_dev: torch.Tensor, route: int, mask_pre: torch.Tensor | None = None):
         """Binarise coding step t (records hdr[k]/coef[k]) into the symbol pool of its group
         ring, on the *copy* stream (the caller's current stream): the records are free
         again once this is done, whatever the arithmetic coder is doing.  Every slot's slice
         type and list size come from the step's routing.
-        qp_dev: [B] int32 slice QPs of this step in a buffer that outlives the launch."""
+        qp_dev: [B] int32 slice QPs of this step in a buffer that outlives the launch.
+        mask_pre: the block masks the step's inter kernels left (_encode_step), if any."""
         B, BS = self.B, self.B * self.S
         r = g & 1
         if j == 0:
@@ -1181,7 +1199,8 @@ class GpuH264Encoder:
                            P(self.cab_cnt), P(self.cab_off), P(self.cab_tot), P(self.cab_pool[r]), self.cab_pool_cap,
                            self.cab_pool_used[r].data_ptr(), self.cab_base[r][j * BS:].data_ptr(),
                            self.cab_total[r][j * BS:].data_ptr(), P(qp_dev), pics[0].slice_type, 1, 1,
-                           int(self.p.eff_t8x8()), P(self.err), self.copy_stream.cuda_stream, route, self.slice_rows)
+                           int(self.p.eff_t8x8()), P(self.err), self.copy_stream.cuda_stream, route, self.slice_rows,
+                           **({"pre": P(mask_pre)} if mask_pre is not None else {}))
 
     def _gpu_cabac_code(self, g: int, t0: int, n: int, qps_d: torch.Tensor, err_to: torch.Tensor | None = None):
         """Arithmetic-code the n frame steps t0 .. t0 + n - 1 of a group (n * B slices) on
@@ -1680,7 +1699,9 @@ class GpuH264Encoder:
             self._prep_step(y, u, v, orders[:, t], orders_d[t], st)
             st["disp_d"] = orders_d[t]
             self.qp.copy_(qps_d[t])
-            self._encode_step(st, self.hdr[k], self.coef[k], cuts_d[t] if (t > 0 and cuts_c[:, t].any()) else None)
+            mpre = self.mask_pre[k] if (cabac_gpu and self.mask_pre is not None and self._use_mask_pre) else None
+            self._encode_step(st, self.hdr[k], self.coef[k], cuts_d[t] if (t > 0 and cuts_c[:, t].any()) else None,
+                              mask_pre=mpre)
             if metrics:
                 P = self._ptr
                 self.hip.sse(B, self.W, self.H, self.p.width, self.p.height, P(self.src[0]), P(self.src[1]),
@@ -1701,7 +1722,7 @@ class GpuH264Encoder:
             with torch.cuda.stream(self.copy_stream):
                 self.copy_stream.wait_event(self.compute_done[k])
                 if cabac_gpu:
-                    self._gpu_cabac_bin(k, gi, jj, t, pics, qpt, idr_ids, qps_d[t], st["route"])
+                    self._gpu_cabac_bin(k, gi, jj, t, pics, qpt, idr_ids, qps_d[t], st["route"], mpre)
                 elif self.entropy == "gpu":
                     self.h_sizes[k].copy_(self.cav_sizes[k], non_blocking=True)
                 else:

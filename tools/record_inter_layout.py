@@ -7,7 +7,10 @@ clips of the padding / AQ and mb_qp_delta flag tests through ``encode``) and
 tests/test_gpu_inter_chroma8.py (suite ``chroma8``: the chroma launch of the inter residual, eight
 MBs per wave; with the record statistics and the mb_qp_delta flag bytes per case) and the
 end-to-end cases of tests/test_gpu_b_block_fetch.py (suite ``bfetch``: the B decision's pre-pass
-and main pass; with the gate's counts and the direct MBs / quadrants of the decoded records).
+and main pass; with the gate's counts and the direct MBs / quadrants of the decoded records) and
+tests/test_gpu_inter_block_mask.py (suite ``mask``: the block masks the inter kernels hand to the
+GPU CABAC path, which the parent's kernels do not write: its bytes, with the record statistics per
+case).
 
 The tests pin the bytes of small encodes, at shapes where the four-MBs-per-wave lane layout can
 go wrong, to what the *parent* build of the kernels emits.  So this recorder never runs on the
@@ -22,6 +25,7 @@ commit, e.g.
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py source tests/golden/source_pass_parent.json
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py chroma8 tests/golden/inter_chroma8_parent.json
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py bfetch tests/golden/b_block_fetch_parent.json
+    MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py mask tests/golden/inter_block_mask_parent.json
 
 The file holds, per case, the arguments (size, frames, clip seed / class, parameter overrides)
 and the SHA-256 of every slot's bitstream.  Per case it also prints what the test asserts
@@ -523,6 +527,36 @@ def record_bfetch(host, path) -> None:
         f.write("\n")
 
 
+def record_mask(host, path) -> None:
+    """Suite ``mask``: per case the per-slot hashes and the record statistics.  The cases, the
+    clips and the statistics are the test's own (the test module reads the golden file when
+    imported, so a first recording starts from an empty one)."""
+    if not os.path.exists(path):
+        with open(path, "w") as f:
+            json.dump(dict(slots=SLOTS, cases=[]), f)
+    from tests import test_gpu_inter_block_mask as T
+
+    rows, tot = [], {}
+    for case in T.CASES:
+        case = json.loads(json.dumps(case))  # as the test will read it
+        enc, res, spy = T.encode(case, poison=False)
+        if spy.mask_pre != {False}:
+            raise SystemExit("this kernel library writes block masks: not the parent's")
+        streams = [bytes(r.bitstream) for r in res]
+        enc.close()
+        stats = T.record_stats(host, streams)
+        vac = [k for k in T._NEED.get(case["id"], ()) if stats[k] == 0]
+        print(case["id"], [len(s) for s in streams], stats, "VACUOUS: " + ",".join(vac) if vac else "", flush=True)
+        for k, n in stats.items():
+            tot[k] = tot.get(k, 0) + n
+        rows.append(dict(case, stats=stats, sha256=[hashlib.sha256(s).hexdigest() for s in streams]))
+    vac = [k for k in T._NEED_ALL if tot[k] == 0]
+    print("all cases", tot, "VACUOUS: " + ",".join(vac) if vac else "", flush=True)
+    with open(path, "w") as f:
+        json.dump(dict(slots=SLOTS, cases=rows), f, indent=1)
+        f.write("\n")
+
+
 def np_isin_any(a, values) -> bool:
     import numpy as np
 
@@ -531,7 +565,7 @@ def np_isin_any(a, values) -> bool:
 
 def main() -> None:
     suite = "inter"
-    if len(sys.argv) == 3 and sys.argv[1] in ("inter", "decide", "gate", "intra", "source", "chroma8", "bfetch"):
+    if len(sys.argv) == 3 and sys.argv[1] in ("inter", "decide", "gate", "intra", "source", "chroma8", "bfetch", "mask"):
         suite = sys.argv.pop(1)
     if len(sys.argv) != 2:
         raise SystemExit(__doc__)
@@ -553,6 +587,9 @@ def main() -> None:
         return
     if suite == "bfetch":
         record_bfetch(host, sys.argv[1])
+        return
+    if suite == "mask":
+        record_mask(host, sys.argv[1])
         return
     if suite == "gate":
         for case in GATE_CASES:
