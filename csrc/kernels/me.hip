@@ -212,6 +212,11 @@ extern "C" void mivc_launch_me(int B, int wmb, int hmb, const uint8_t* src_y, co
     fprintf(stderr, "mivc_launch_me: a routed search needs the resident half-sample pool\n");
     abort();
   }
+  // the search reads a vector pair as one dword
+  if ((reinterpret_cast<uintptr_t>(pred_mv) | reinterpret_cast<uintptr_t>(cost_mv) | reinterpret_cast<uintptr_t>(seed_mv)) & 3) {
+    fprintf(stderr, "mivc_launch_me: pred_mv / cost_mv / seed_mv must be 4-byte aligned\n");
+    abort();
+  }
   if (!(planes_ready && hp_buf)) mivc_launch_me_halfpel(B, W, H, ref_y, hp, stream, nullptr, 0);
   MeArgs a;
   a.g = Geom{B, wmb, hmb, W, H};

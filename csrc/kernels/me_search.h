@@ -22,6 +22,12 @@
 // rounded average of two samples of the 4 planes (kQOff), so the four 16-lane
 // candidate groups of a wave never diverge.
 //
+// Issue structure (the kernel is bound by vector instruction issue, profiles/me_scalar_uniform.md):
+// nearly everything but the pixels is the same in all 64 lanes -- MB coordinates, vectors and
+// their costs, the centre, window and plane origins, the inside tests -- and is kept in scalar
+// registers (uni()); each phase asks once whether all it reads lies inside the picture and then
+// loads without clamps, a 32-bit lane offset from scalar bases.
+//
 // A search is one wave64 per macroblock.  Launches that search every MB (no gate) run one
 // single-wave workgroup per MB; the workgroup id is remapped so each XCD walks a contiguous
 // run of MBs (window rows are shared through that XCD's L2).  Gated launches (B pictures,
@@ -90,8 +96,16 @@ inline __constant__ short kQOff[16][2] = {  // (inline: one opaque definition pe
 };
 #undef QO
 
-__device__ __forceinline__ int wave_min_key(int key) { return min64(key); }
-__device__ __forceinline__ int wave_sum(int v) { return sum64(v); }
+// A wave-uniform value as a scalar: what is computed from it (vector costs, clamps, the inside
+// tests, addresses) then runs on the scalar unit, and conditions on it are branches instead of
+// exec masks.  The wave reductions end in lane swaps, so their results count as divergent until
+// pinned; a value the compiler already holds in a scalar register passes through for free.
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ int wave_min_key(int key) { return uni(min64(key)); }
+__device__ __forceinline__ int wave_sum(int v) { return uni(sum64(v)); }
+// a vector pair (x, y) of [.., 2] int16 is one aligned dword; the halves of a pinned one
+__device__ __forceinline__ int mv_pair_x(int w) { return static_cast<int16_t>(w & 0xFFFF); }
+__device__ __forceinline__ int mv_pair_y(int w) { return w >> 16; }
 
 // LDS of one workgroup, sized for the largest radius its kernel instance accepts
 // (me_p16x16<8> fits 31 workgroups per CU by LDS instead of 22 for radius 16).
@@ -146,6 +160,33 @@ __device__ __forceinline__ void stage_window(SH& S, const uint8_t* ref, int W, i
     int i = lane + 64 * k;
     int r = i / words, w = i - r * words;
     if (i < n) S.win[r * kWinPitch + w] = v[k];
+  }
+}
+
+// The same LDS image for a window that lies wholly inside the picture, its size known at compile
+// time: no clamps, and a batch of loads is 64 / WORDS whole rows, so a lane keeps one (row, word)
+// for all its loads -- one 32-bit offset from a scalar base that steps by whole rows, and LDS
+// stores a constant apart.  `base`: the window's first aligned word (wave-uniform).
+template <int ROWS, int WORDS, class SH>
+__device__ __forceinline__ void stage_window_in(SH& S, const uint8_t* base, int W, int lane) {
+  constexpr int RPK = 64 / WORDS;                // rows per batch
+  constexpr int NK = (ROWS + RPK - 1) / RPK;
+  constexpr int LAST = ROWS - RPK * (NK - 1);    // rows of the last batch
+  static_assert(NK <= SH::kLoads, "window batches");
+  const int r0 = lane / WORDS, w0 = lane - r0 * WORDS;
+  const bool live = r0 < RPK, live_last = r0 < LAST;
+  // lanes without an item load the batch's first word again instead of branching around the load
+  const uint32_t off = live ? static_cast<uint32_t>(r0 * W + 4 * w0) : 0u;
+  const uint32_t off_last = live_last ? off : 0u;
+  uint32_t v[NK];
+#pragma unroll
+  for (int k = 0; k < NK; ++k)
+    v[k] = *reinterpret_cast<const uint32_t*>(base + static_cast<size_t>(RPK * k) * W + (k == NK - 1 ? off_last : off));
+  uint32_t* dst = S.win + r0 * kWinPitch + w0;
+  if (live) {
+#pragma unroll
+    for (int k = 0; k < NK - 1; ++k) dst[RPK * k * kWinPitch] = v[k];
+    if (live_last) dst[RPK * (NK - 1) * kWinPitch] = v[NK - 1];
   }
 }
 
@@ -275,13 +316,14 @@ __device__ __forceinline__ void me_mb(const MeArgs a, int slot_run, int mb_run, 
       if (rr.kind != a.want || (a.role < RO_L1 && a.role >= rr.n0)) return;
     }
   }
-  const size_t rslot = route_index(a.rt, a.nbuf, slot, a.role);
+  // (a pool index read from the route row's bytes: pinned, or every reference address is a vector)
+  const size_t rslot = static_cast<size_t>(uni(static_cast<int>(route_index(a.rt, a.nbuf, slot, a.role))));
   const uint8_t* src = a.src_y + slot * g.ysize();
   const uint8_t* ref = a.ref_y + rslot * g.ysize();
   const int W = g.W, H = g.H;
   int lambda = lambda_run;
   if constexpr (SPAN == 1) {
-    const int qp = clampi(a.qp[slot] + (a.aq ? a.aq[static_cast<size_t>(slot) * nmb + mb] : 0), 0, 51);
+    const int qp = uni(clampi(a.qp[slot] + (a.aq ? a.aq[static_cast<size_t>(slot) * nmb + mb] : 0), 0, 51));
     lambda = h264::kLambda[qp];
   }
   const int R = a.range < MAXR ? a.range : MAXR;
@@ -306,47 +348,82 @@ __device__ __forceinline__ void me_mb(const MeArgs a, int slot_run, int mb_run, 
   MPROF(0);
   // ---- phase 0: source MB, its intra neighbours, candidate vectors (one batch of loads)
   const int r4 = lane >> 2, c4 = (lane & 3) * 4;
-  const uint32_t my_src = *reinterpret_cast<const uint32_t*>(src + static_cast<size_t>(Y0 + r4) * W + X0 + c4);
+  // the lane's 4 samples of a 16x16 block, as an offset from the block's (wave-uniform) origin
+  const uint32_t loff = static_cast<uint32_t>(r4 * W + c4);
+  const uint32_t my_src = *reinterpret_cast<const uint32_t*>(src + static_cast<size_t>(Y0) * W + X0 + loff);
   int nbv = 0;
   if (lane < 16) nbv = my > 0 ? src[static_cast<size_t>(Y0 - 1) * W + X0 + lane] : 0;
   else if (lane < 32) nbv = mx > 0 ? src[static_cast<size_t>(Y0 + lane - 16) * W + X0 - 1] : 0;
   else if (lane == 32) nbv = (mx > 0 && my > 0) ? src[static_cast<size_t>(Y0 - 1) * W + X0 - 1] : 0;
   int pmx = 0, pmy = 0;
   int cand_x[6] = {0, 0, 0, 0, 0, 0}, cand_y[6] = {0, 0, 0, 0, 0, 0};
+  // the vectors are wave-uniform: each pair is one dword at a uniform address, kept scalar
+  const size_t omb = static_cast<size_t>(slot) * nmb + mb;
+  // (a neighbour outside the picture reads the MB's own pair instead, so the loads go out
+  // together; its candidate stays the zero vector)
+  int w_seed = 0, w_own = 0, w_cost = 0, w_left = 0, w_top = 0, w_right = 0;
+  if (a.seed_mv) w_seed = reinterpret_cast<const int*>(a.seed_mv)[omb];
+  if (a.pred_mv) {
+    const int* pm = reinterpret_cast<const int*>(a.pred_mv) + omb;
+    w_own = pm[0];
+    w_left = pm[mx > 0 ? -1 : 0];
+    w_top = pm[my > 0 ? -g.wmb : 0];
+    w_right = pm[mx < g.wmb - 1 ? 1 : 0];
+    if (a.cost_mv) w_cost = reinterpret_cast<const int*>(a.cost_mv)[omb];
+  }
   if (a.seed_mv) {
-    const size_t so = (static_cast<size_t>(slot) * nmb + mb) * 2;
-    cand_x[5] = (a.seed_mv[so] + 2) >> 2;
-    cand_y[5] = (a.seed_mv[so + 1] + 2) >> 2;
+    w_seed = uni(w_seed);
+    cand_x[5] = (mv_pair_x(w_seed) + 2) >> 2;
+    cand_y[5] = (mv_pair_y(w_seed) + 2) >> 2;
   }
   if (a.pred_mv) {
-    const int16_t* pm = a.pred_mv + static_cast<size_t>(slot) * nmb * 2;
-    pmx = pm[mb * 2];
-    pmy = pm[mb * 2 + 1];
+    w_own = uni(w_own), w_left = uni(w_left), w_top = uni(w_top), w_right = uni(w_right);
+    pmx = mv_pair_x(w_own);
+    pmy = mv_pair_y(w_own);
     cand_x[0] = (pmx + 2) >> 2;
     cand_y[0] = (pmy + 2) >> 2;
     if (a.cost_mv) {
-      pmx = a.cost_mv[(static_cast<size_t>(slot) * nmb + mb) * 2];
-      pmy = a.cost_mv[(static_cast<size_t>(slot) * nmb + mb) * 2 + 1];
+      w_cost = uni(w_cost);
+      pmx = mv_pair_x(w_cost);
+      pmy = mv_pair_y(w_cost);
     }
-    if (mx > 0) { cand_x[1] = (pm[(mb - 1) * 2] + 2) >> 2; cand_y[1] = (pm[(mb - 1) * 2 + 1] + 2) >> 2; }
-    if (my > 0) { cand_x[2] = (pm[(mb - g.wmb) * 2] + 2) >> 2; cand_y[2] = (pm[(mb - g.wmb) * 2 + 1] + 2) >> 2; }
-    if (mx < g.wmb - 1) { cand_x[3] = (pm[(mb + 1) * 2] + 2) >> 2; cand_y[3] = (pm[(mb + 1) * 2 + 1] + 2) >> 2; }
+    if (mx > 0) { cand_x[1] = (mv_pair_x(w_left) + 2) >> 2; cand_y[1] = (mv_pair_y(w_left) + 2) >> 2; }
+    if (my > 0) { cand_x[2] = (mv_pair_x(w_top) + 2) >> 2; cand_y[2] = (mv_pair_y(w_top) + 2) >> 2; }
+    if (mx < g.wmb - 1) { cand_x[3] = (mv_pair_x(w_right) + 2) >> 2; cand_y[3] = (mv_pair_y(w_right) + 2) >> 2; }
   }
   uint32_t cref[6];
+  bool cand_in = true;  // every candidate block lies inside the picture
 #pragma unroll
   for (int k = 0; k < 6; ++k) {
     cand_x[k] = clampi(cand_x[k], -128, 128);
     cand_y[k] = clampi(cand_y[k], -128, 128);
-    const uint8_t* rp = ref + static_cast<size_t>(clampi(Y0 + r4 + cand_y[k], 0, H - 1)) * W;
-    const int xs = X0 + c4 + cand_x[k];
-    uint32_t w = 0;
-    if (xs >= 0 && xs + 4 <= W) {
-      w = load4u(rp, xs);
-    } else {
+    cand_in = cand_in && X0 + cand_x[k] >= 0 && X0 + cand_x[k] + 16 <= W && Y0 + cand_y[k] >= 0 && Y0 + cand_y[k] + 16 <= H;
+  }
+  if (cand_in) {
+    // no clamps: two aligned words at the lane's block offset from a scalar base per candidate
+    // (an aligned candidate reads its word twice instead of the word after its row)
 #pragma unroll
-      for (int b = 0; b < 4; ++b) w |= static_cast<uint32_t>(rp[clampi(xs + b, 0, W - 1)]) << (8 * b);
+    for (int k = 0; k < 6; ++k) {
+      const int xs0 = X0 + cand_x[k], sh = xs0 & 3;
+      const uint8_t* b0 = ref + static_cast<size_t>(Y0 + cand_y[k]) * W + (xs0 & ~3);
+      const uint8_t* b1 = b0 + (sh ? 4 : 0);
+      cref[k] = __builtin_amdgcn_alignbyte(*reinterpret_cast<const uint32_t*>(b1 + loff),
+                                           *reinterpret_cast<const uint32_t*>(b0 + loff), sh);
     }
-    cref[k] = w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const uint8_t* rp = ref + static_cast<size_t>(clampi(Y0 + r4 + cand_y[k], 0, H - 1)) * W;
+      const int xs = X0 + c4 + cand_x[k];
+      uint32_t w = 0;
+      if (xs >= 0 && xs + 4 <= W) {
+        w = load4u(rp, xs);
+      } else {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) w |= static_cast<uint32_t>(rp[clampi(xs + b, 0, W - 1)]) << (8 * b);
+      }
+      cref[k] = w;
+    }
   }
   S.src[lane] = my_src;
   if (lane < 33) S.nb[lane] = nbv;
@@ -452,9 +529,21 @@ __device__ __forceinline__ void me_mb(const MeArgs a, int slot_run, int mb_run, 
   int wx = X0 + cx - R - kML;
   int xa = wx & ~3, sh0 = wx - xa;
   const int wwords = (wrows + 3) / 4 + 1;
-  if (R == 8) stage_window<(16 + 16 + kML + kMR + 3) / 4 + 1>(S, ref, W, H, xa, Y0 + cy - R - kML, wrows, wwords, lane);
-  else if (R == 4) stage_window<(16 + 8 + kML + kMR + 3) / 4 + 1>(S, ref, W, H, xa, Y0 + cy - R - kML, wrows, wwords, lane);
-  else stage_window<0>(S, ref, W, H, xa, Y0 + cy - R - kML, wrows, wwords, lane);
+  const int wy = Y0 + cy - R - kML;
+  constexpr int kRows8 = 16 + 16 + kML + kMR, kWords8 = (kRows8 + 3) / 4 + 1;
+  constexpr int kRows4 = 16 + 8 + kML + kMR, kWords4 = (kRows4 + 3) / 4 + 1;
+  // one test for the phase: every word of the window inside the picture
+  const bool win_in = xa >= 0 && xa + 4 * wwords <= W && wy >= 0 && wy + wrows <= H;
+  const uint8_t* wbase = ref + static_cast<ptrdiff_t>(wy) * W + xa;
+  if (R == 8) {
+    if (win_in) stage_window_in<kRows8, kWords8>(S, wbase, W, lane);
+    else stage_window<kWords8>(S, ref, W, H, xa, wy, wrows, wwords, lane);
+  } else if (R == 4) {
+    if (win_in) stage_window_in<kRows4, kWords4>(S, wbase, W, lane);
+    else stage_window<kWords4>(S, ref, W, H, xa, wy, wrows, wwords, lane);
+  } else {
+    stage_window<0>(S, ref, W, H, xa, wy, wrows, wwords, lane);
+  }
   __syncthreads();
 
   MPROF(2);
@@ -493,7 +582,7 @@ __device__ __forceinline__ void me_mb(const MeArgs a, int slot_run, int mb_run, 
   const bool zero_outside = cx < -R || cx > R || cy < -R || cy > R;
   if (zero_outside) {
     int sad = wave_sum(static_cast<int>(sad4(my_src, *reinterpret_cast<const uint32_t*>(
-                                                          ref + static_cast<size_t>(Y0 + r4) * W + X0 + c4), 0)));
+                                                          ref + static_cast<size_t>(Y0) * W + X0 + loff), 0)));
     int cost = sad + lambda * (mvbits_se(-pmx) + mvbits_se(-pmy));
     int key = (cost << 12) | 4095;
     best_key = key < best_key ? key : best_key;
@@ -527,39 +616,67 @@ __device__ __forceinline__ void me_mb(const MeArgs a, int slot_run, int mb_run, 
     // 4 planes (G from the reference itself, b / h / j from hp) x 20 rows x 6 words =
     // 480 words, one batch of loads; lane item i -> (plane, row, word)
     uint32_t v[8];
+    // one test for the phase: no row or column of the four regions needs a clamp (the half-sample
+    // planes' margin makes gin imply xin).  Then a batch is 10 whole rows of one plane (60 lanes):
+    // plane and row step are compile-time, the lane keeps one (row, word) -- two 32-bit offsets,
+    // for the two pitches -- and the bases are scalar.
+    const bool planes_in = gin && y0 >= 0 && y0 + 20 <= H;
+    const int pr0 = lane / 6, pw0 = lane - pr0 * 6;
+    const bool plive = lane < 60;
+    if (planes_in) {
+      const uint32_t og = plive ? static_cast<uint32_t>(pr0 * W + 4 * pw0) : 0u;
+      const uint32_t oh = plive ? static_cast<uint32_t>(pr0 * PW + 4 * pw0) : 0u;
+      const uint8_t* gb = ref + static_cast<size_t>(y0) * W + xa;
+      const uint8_t* hb = hp + static_cast<size_t>(y0 + kHpMargin) * PW + xa + kHpMargin;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int i = lane + 64 * k;
-      const int pl = i / 120, rem = i - pl * 120, r = rem / 6, w = rem - r * 6;
-      uint32_t word = 0;
-      if (i < 480) {
-        if (pl == 0) {
-          const uint8_t* row = ref + static_cast<size_t>(clampi(y0 + r, 0, H - 1)) * W;
-          if (gin) {
-            word = *reinterpret_cast<const uint32_t*>(row + xa + 4 * w);
+      for (int k = 0; k < 8; ++k) {
+        const int pl = k >> 1, row = 10 * (k & 1);
+        v[k] = pl == 0 ? *reinterpret_cast<const uint32_t*>(gb + static_cast<size_t>(row) * W + og)
+                       : *reinterpret_cast<const uint32_t*>(hb + static_cast<size_t>(pl - 1) * PW * PH +
+                                                            static_cast<size_t>(row) * PW + oh);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int i = lane + 64 * k;
+        const int pl = i / 120, rem = i - pl * 120, r = rem / 6, w = rem - r * 6;
+        uint32_t word = 0;
+        if (i < 480) {
+          if (pl == 0) {
+            const uint8_t* row = ref + static_cast<size_t>(clampi(y0 + r, 0, H - 1)) * W;
+            if (gin) {
+              word = *reinterpret_cast<const uint32_t*>(row + xa + 4 * w);
+            } else {
+#pragma unroll
+              for (int q = 0; q < 4; ++q) word |= static_cast<uint32_t>(row[clampi(xa + 4 * w + q, 0, W - 1)]) << (8 * q);
+            }
           } else {
+            const int yy = clampi(y0 + r, -kHpMargin, H + kHpMargin - 1) + kHpMargin;
+            const uint8_t* row = hp + static_cast<size_t>(pl - 1) * PW * PH + static_cast<size_t>(yy) * PW;
+            if (xin) {
+              word = *reinterpret_cast<const uint32_t*>(row + xa + kHpMargin + 4 * w);
+            } else {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) word |= static_cast<uint32_t>(row[clampi(xa + 4 * w + q, 0, W - 1)]) << (8 * q);
-          }
-        } else {
-          const int yy = clampi(y0 + r, -kHpMargin, H + kHpMargin - 1) + kHpMargin;
-          const uint8_t* row = hp + static_cast<size_t>(pl - 1) * PW * PH + static_cast<size_t>(yy) * PW;
-          if (xin) {
-            word = *reinterpret_cast<const uint32_t*>(row + xa + kHpMargin + 4 * w);
-          } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-              word |= static_cast<uint32_t>(row[clampi(xa + 4 * w + q, -kHpMargin, W + kHpMargin - 1) + kHpMargin]) << (8 * q);
+              for (int q = 0; q < 4; ++q)
+                word |= static_cast<uint32_t>(row[clampi(xa + 4 * w + q, -kHpMargin, W + kHpMargin - 1) + kHpMargin]) << (8 * q);
+            }
           }
         }
+        v[k] = word;
       }
-      v[k] = word;
     }
     wave_sync();  // last window reads (integer search) before the planes overwrite it
+    if (planes_in) {
+      if (plive) {
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int i = lane + 64 * k;
-      if (i < 480) S.P32[i] = v[k];  // plane p starts at word 120 * p; rows of 6 words
+        for (int k = 0; k < 8; ++k) S.P32[60 * k + lane] = v[k];  // batch k: words 60 k .. 60 k + 59
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int i = lane + 64 * k;
+        if (i < 480) S.P32[i] = v[k];  // plane p starts at word 120 * p; rows of 6 words
+      }
     }
   }
   if (lane < 4) S.P32[4 * kPlane / 4 + lane] = 0;
@@ -592,16 +709,23 @@ __device__ __forceinline__ void me_mb(const MeArgs a, int slot_run, int mb_run, 
 #pragma unroll
   for (int t = 0; t < 4; ++t) cS[t] = -__builtin_amdgcn_mfma_f32_16x16x16f16(negH, as_h(S.src[(t * 4 + mg) * 4 + mb_b]),
                                                                              v4f{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+  // what a lane keeps over the five rounds: the byte offset of its block's row mg in the plane
+  // block (plane sample (u, v) = (4 mb_b + 2, mg + 2), see pred4); a round adds its candidate's
+  const int sub_base = (mg + 2) * kPP + mb_b * 4 + 2 + psh;
   // SATD of this lane's candidate (quarter offsets (dqx, dqy) relative to (4bx, 4by))
   auto satd_cand = [&](int dqx, int dqy) -> int {
     const int q = (dqy & 3) * 4 + (dqx & 3), ox = dqx >> 2, oy = dqy >> 2;
-    const int offa = S.qoff[2 * q], offb = S.qoff[2 * q + 1];
-    const int u = mb_b * 4 + ox + 2;
+    // the candidate's two taps of block row 0; block row t lies 4 plane rows = 4 * kPP bytes =
+    // 24 words further on, so the word index and the byte shift hold for all four rows
+    const int ca = sub_base + oy * kPP + ox + S.qoff[2 * q], cb = sub_base + oy * kPP + ox + S.qoff[2 * q + 1];
+    const uint32_t* pa = S.P32 + (ca >> 2);
+    const uint32_t* pb = S.P32 + (cb >> 2);
     float acc = 0.f;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      const v4f d = __builtin_amdgcn_mfma_f32_16x16x16f16(negH, as_h(pred4(u, t * 4 + mg + oy + 2, offa, offb)), cS[t],
-                                                          0, 0, 0);
+      const uint32_t p4 = avg4b(__builtin_amdgcn_alignbyte(pa[kPP * t + 1], pa[kPP * t], ca & 3),
+                                __builtin_amdgcn_alignbyte(pb[kPP * t + 1], pb[kPP * t], cb & 3));
+      const v4f d = __builtin_amdgcn_mfma_f32_16x16x16f16(negH, as_h(p4), cS[t], 0, 0, 0);
       acc += __builtin_fabsf(d[0]) + __builtin_fabsf(d[1]) + __builtin_fabsf(d[2]) + __builtin_fabsf(d[3]);
     }
     // the candidate's 16 lanes: block bits 0-1 and row-group bits 4-5
@@ -667,7 +791,7 @@ __device__ __forceinline__ void me_mb(const MeArgs a, int slot_run, int mb_run, 
   {
     int dqx = best_mvx - 4 * bx, dqy = best_mvy - 4 * by;
     int q = (dqy & 3) * 4 + (dqx & 3), ox = dqx >> 2, oy = dqy >> 2;
-    int offa = S.qoff[2 * q], offb = S.qoff[2 * q + 1];
+    int offa = kQOff[q][0], offb = kQOff[q][1];  // q is wave-uniform here: a scalar load
     reinterpret_cast<uint32_t*>(a.out_pred + o * 256)[lane] = pred4(c4 + ox + 2, r4 + oy + 2, offa, offb);
   }
   MPROF(8);

@@ -18,8 +18,9 @@ __device__ __forceinline__ int mvbits_se(int v) {
   return 2 * (31 - __clz(x)) + 1;
 }
 
-// per-byte rounding average (a + b + 1) >> 1 of two packed words
-__device__ __forceinline__ uint32_t avg4b(uint32_t a, uint32_t b) { return (a | b) - (((a ^ b) >> 1) & 0x7F7F7F7Fu); }
+// per-byte rounding average (a + b + 1) >> 1 of two packed words: v_lerp_u8, whose third operand
+// supplies each byte's rounding bit
+__device__ __forceinline__ uint32_t avg4b(uint32_t a, uint32_t b) { return __builtin_amdgcn_lerp(a, b, 0x01010101u); }
 
 // implicit weighted bi-prediction of 4 packed samples (8.4.2.3.2 with logWD 5, offsets 0):
 // (a * (64 - w1) + b * w1 + 32) >> 6; w1 = 32 is the plain rounded average

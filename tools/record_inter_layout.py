@@ -10,7 +10,9 @@ end-to-end cases of tests/test_gpu_b_block_fetch.py (suite ``bfetch``: the B dec
 and main pass; with the gate's counts and the direct MBs / quadrants of the decoded records) and
 tests/test_gpu_inter_block_mask.py (suite ``mask``: the block masks the inter kernels hand to the
 GPU CABAC path, which the parent's kernels do not write: its bytes, with the record statistics per
-case).
+case) and tests/test_gpu_me_uniform_encode.py (suite ``me``: whole encodes through the 16x16 motion
+search, whose wave-uniform work moved to the scalar unit: P only, B pictures with temporal direct,
+three references with weighted P, b-pyramid, CAVLC, one HEVC encode).
 
 The tests pin the bytes of small encodes, at shapes where the four-MBs-per-wave lane layout can
 go wrong, to what the *parent* build of the kernels emits.  So this recorder never runs on the
@@ -26,6 +28,7 @@ commit, e.g.
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py chroma8 tests/golden/inter_chroma8_parent.json
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py bfetch tests/golden/b_block_fetch_parent.json
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py mask tests/golden/inter_block_mask_parent.json
+    MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py me tests/golden/me_uniform_parent.json
 
 The file holds, per case, the arguments (size, frames, clip seed / class, parameter overrides)
 and the SHA-256 of every slot's bitstream.  Per case it also prints what the test asserts
@@ -277,6 +280,33 @@ BFETCH_CASES = [
     _bf("80x48-spatial-fast", 80, 48, 9, 96, "default", _BF_ALL, qp=26, weightb=True, refs=1, direct="spatial"),
     _bf("176x144-spatial-wavefront-gate", 176, 144, 7, 97, "default", _BF_ALL, qp=26, weightb=True, refs=1,
         direct="spatial", spatial_wavefront=True, spatial_gate=True),
+]
+
+# The 16x16 motion search in whole encodes (me_search.h): every picture type and list search that
+# calls it, at 15 MBs (5 per row: no MB has its window inside the picture), 49 (7 x 7) and 99.
+# 112x112 and 176x144 have MBs on both the interior and the edge path of every phase.
+_MQ = dict(crf=None, qp=26)
+ME_CASES = [
+    dict(id="h264-80x48-p", codec="h264", width=80, height=48, frames=5, seed=101, kind="default",
+         params=dict(bframes=0, refs=1, **_MQ)),
+    dict(id="h264-176x144-p-pan", codec="h264", width=176, height=144, frames=6, seed=102, kind="pan-fast",
+         params=dict(bframes=0, refs=1, aq_strength=1.0, **_MQ)),
+    dict(id="h264-112x112-b3-temporal", codec="h264", width=112, height=112, frames=9, seed=103, kind="default",
+         params=dict(bframes=3, direct="temporal", refs=1, **_MQ)),
+    dict(id="h264-176x144-b3-temporal-zoom", codec="h264", width=176, height=144, frames=9, seed=104, kind="zoom",
+         params=dict(bframes=3, direct="temporal", weightb=True, **_MQ)),
+    dict(id="h264-176x144-p-refs3-weightp-fade", codec="h264", width=176, height=144, frames=7, seed=105, kind="fade",
+         params=dict(bframes=0, refs=3, weightp=True, **_MQ)),
+    dict(id="h264-112x112-p-refs3-weightp", codec="h264", width=112, height=112, frames=6, seed=106, kind="default",
+         params=dict(bframes=0, refs=3, weightp=True, ref_gate=0, **_MQ)),
+    dict(id="h264-176x144-b3-pyramid", codec="h264", width=176, height=144, frames=9, seed=107, kind="default",
+         params=dict(bframes=3, pyramid=True, refs=2, **_MQ)),
+    dict(id="h264-80x48-b3-cavlc", codec="h264", width=80, height=48, frames=9, seed=108, kind="default",
+         params=dict(bframes=3, cabac=False, **_MQ)),
+    dict(id="h264-176x144-p-cavlc", codec="h264", width=176, height=144, frames=5, seed=109, kind="pan-fast",
+         params=dict(bframes=0, cabac=False, **_MQ)),
+    dict(id="hevc-176x144-p", codec="hevc", width=176, height=144, frames=6, seed=110, kind="default",
+         params=dict(bframes=0, crf=None, qp=30)),
 ]
 
 INTRA_KINDS = (0, 1, 4, 8)
@@ -565,7 +595,7 @@ def np_isin_any(a, values) -> bool:
 
 def main() -> None:
     suite = "inter"
-    if len(sys.argv) == 3 and sys.argv[1] in ("inter", "decide", "gate", "intra", "source", "chroma8", "bfetch", "mask"):
+    if len(sys.argv) == 3 and sys.argv[1] in ("inter", "decide", "gate", "intra", "source", "chroma8", "bfetch", "mask", "me"):
         suite = sys.argv.pop(1)
     if len(sys.argv) != 2:
         raise SystemExit(__doc__)
@@ -599,7 +629,7 @@ def main() -> None:
             vac = [k for k in gate_expect(case) if counts[k] == 0]
             print(case["id"], [len(s) for s in streams], counts, "VACUOUS: " + ",".join(vac) if vac else "", flush=True)
             rows.append(dict(case, counts=counts, sha256=[hashlib.sha256(s).hexdigest() for s in streams]))
-    for case in ([] if suite == "gate" else CASES if suite == "inter" else DECIDE_CASES):
+    for case in ([] if suite == "gate" else CASES if suite == "inter" else ME_CASES if suite == "me" else DECIDE_CASES):
         if suite == "inter":
             enc, res = encode_case(case)
         else:
@@ -609,7 +639,8 @@ def main() -> None:
                 print(case["id"], "DROPPED:", repr(e), flush=True)
                 continue
         streams = [bytes(r.bitstream) for r in res]
-        stats = record_stats(host, streams) if suite == "inter" else decide_stats(host, case, enc, streams)
+        stats = (record_stats(host, streams) if suite == "inter" else {} if suite == "me" else
+                 decide_stats(host, case, enc, streams))
         enc.close()
         print(case["id"], [len(s) for s in streams], stats, flush=True)
         rows.append(dict(case, sha256=[hashlib.sha256(s).hexdigest() for s in streams]))

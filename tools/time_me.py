@@ -20,15 +20,21 @@ def main():
     P = lambda t: t.data_ptr()  # noqa: E731
     s = torch.cuda.current_stream().cuda_stream
     enc.qp.fill_(27)
+    # slot-contiguous copies of the reference and its half-sample planes (the encoder keeps pools
+    # [B, nbuf, plane], which only a routed launch can address)
+    ref = enc.rec[0][0].contiguous()
+    hp = torch.empty(B * enc.hp_bytes + 64, dtype=torch.uint8, device=ref.device)
+    enc.hip.me_halfpel(B, enc.W, enc.H, P(ref), P(hp), s)
+    torch.cuda.synchronize()
 
     def run(r, sp, n=5):
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        enc.hip.me(B, enc.wmb, enc.hmb, P(enc.src[0]), P(enc.rec[0][0]), P(enc.prev_mv), P(enc.mv), P(enc.me_cost),
-                   P(enc.pred), P(enc.intra_cost), P(enc.qp), r, sp, s, P(enc.me_hp))
+        enc.hip.me(B, enc.wmb, enc.hmb, P(enc.src[0]), P(ref), P(enc.prev_mv), P(enc.mv), P(enc.me_cost),
+                   P(enc.pred), P(enc.intra_cost), P(enc.qp), r, sp, s, P(hp), 0, 1)
         ev0.record()
         for _ in range(n):
-            enc.hip.me(B, enc.wmb, enc.hmb, P(enc.src[0]), P(enc.rec[0][0]), P(enc.prev_mv), P(enc.mv),
-                       P(enc.me_cost), P(enc.pred), P(enc.intra_cost), P(enc.qp), r, sp, s, P(enc.me_hp))
+            enc.hip.me(B, enc.wmb, enc.hmb, P(enc.src[0]), P(ref), P(enc.prev_mv), P(enc.mv),
+                       P(enc.me_cost), P(enc.pred), P(enc.intra_cost), P(enc.qp), r, sp, s, P(hp), 0, 1)
         ev1.record()
         torch.cuda.synchronize()
         return ev0.elapsed_time(ev1) / n
