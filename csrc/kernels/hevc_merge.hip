@@ -73,7 +73,12 @@ __global__ __launch_bounds__(64) void hevc_merge_refine(MergeRefineArgs a) {
   int best = c_me, bx_ = cx, by_ = cy;
   for (int j = 0; j < nk; ++j) {
     if (kx[j] == cx && ky[j] == cy) {  // the searched vector is itself a merge candidate
-      best = min(best, c_me - lambda * (mvbits_se(cx - pmx) + mvbits_se(cy - pmy)) + lambda * (1 + j));
+      const int cst = c_me - lambda * (mvbits_se(cx - pmx) + mvbits_se(cy - pmy)) + lambda * (1 + j);
+      if (cst < best) {  // also against an earlier candidate that had beaten the search: the vector goes with its price
+        best = cst;
+        bx_ = cx;
+        by_ = cy;
+      }
       continue;
     }
     uint32_t ps[4];

@@ -4,7 +4,11 @@ b_spatial_fixup, b_spatial_decide).  A decoder round trip cannot see a changed d
 every case is checked two ways: the CPU decoder's reconstruction of the emitted stream equals
 the encoder's, bit for bit, and the SHA-256 of every slot's bitstream equals the value that the
 parent commit's kernels emitted for the same arguments, recorded on the GPU by
-``tools/record_inter_layout.py decide`` into tests/golden/decide_layout_parent.json.
+``tools/record_inter_layout.py decide`` into tests/golden/decide_layout_parent.json.  Whether the
+HEVC decisions are the right ones is checked elsewhere: tests/test_gpu_hevc_merge_model.py holds
+every output of the merge kernels against the numpy model of tests/ref_models_hevc_merge.py.
+(The two ``merge_exact=False`` cases were re-recorded when that comparison found
+``hevc_merge_refine`` keeping a neighbour's vector at the searched vector's merge price.)
 
 HEVC sizes are padded to the CTB, so every wave of four 16x16 blocks is full; the shapes make
 waves straddle block rows (6 and 10 blocks per row) and put blocks on CTU edges of both CTU
