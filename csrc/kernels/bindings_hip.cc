@@ -135,14 +135,16 @@ int mivc_launch_scale(const void* in, int w, int h, long long in_stride, long lo
 void mivc_launch_hevc_intra(int B, int W, int H, const uint16_t* sy, const uint16_t* su, const uint16_t* sv,
                             uint16_t* ry, uint16_t* ru, uint16_t* rv, void* ctu, void* cu, int16_t* cy, int16_t* cu_,
                             int16_t* cv, const int* qp, const int8_t* run, int* cand, int bd, int analyze, int recon,
-                            int* err, int sdh, const uint8_t* ctb_mask, void* stream, int ctu64);
+                            int* err, int sdh, const uint8_t* ctb_mask, void* stream, int ctu64, int rdoq, int rdoq_lam);
 void mivc_launch_hevc_inter(int B, int W, int H, const uint16_t* sy, const uint16_t* su, const uint16_t* sv,
                             const uint16_t* fy, const uint16_t* fu, const uint16_t* fv, uint16_t* ry, uint16_t* ru,
                             uint16_t* rv, void* ctu, void* cu, int16_t* cy, int16_t* cu_, int16_t* cv, const int* qp,
                             const int8_t* run, const int* cand, const int16_t* mv, const int* me_cost, int bd,
                             int tu_split, int sdh, int intra_bias, void* stream, const int16_t* mvb,
                             const uint8_t* dirb, const uint16_t* f1y, const uint16_t* f1u, const uint16_t* f1v,
-                            const int16_t* wp, const uint16_t* const* xref, const int16_t* mv8);
+                            const int16_t* wp, const uint16_t* const* xref, const int16_t* mv8, int rdoq, int rdoq_lam);
+int mivc_launch_hevc_tq_probe(int nblk, const int* res, int16_t* lev, int* rec, int* flag, int log2n, int bd, int qp,
+                              int intra, int dst, int scan, int sdh, int rdoq, int rdoq_lam, int mfma, void* stream);
 void mivc_launch_hevc_b(int mode, int B, int wmb, int hmb, const uint8_t* src_y, const uint8_t* ref0, const uint8_t* ref1,
                         const uint8_t* hp0, const uint8_t* hp1, const int16_t* mv0, const int16_t* mv1, const int* cost0,
                         const int* cost1, const int16_t* pm0, const int16_t* pm1, const int16_t* tmv, const uint8_t* tdir,
@@ -601,21 +603,24 @@ PYBIND11_MODULE(_hip, m) {
   m.def("hevc_intra", [](int B, int W, int H, uintptr_t sy, uintptr_t su, uintptr_t sv, uintptr_t ry, uintptr_t ru,
                          uintptr_t rv, uintptr_t ctu, uintptr_t cu, uintptr_t cy, uintptr_t cu_, uintptr_t cv,
                          uintptr_t qp, uintptr_t run, uintptr_t cand, int bd, int analyze, int recon, uintptr_t err,
-                         uintptr_t stream, int sdh, uintptr_t ctb_mask, int ctu64) {
+                         uintptr_t stream, int sdh, uintptr_t ctb_mask, int ctu64, int rdoq, int rdoq_lam) {
+    if (rdoq < 0 || rdoq > 2 || rdoq_lam < 0 || rdoq_lam > 1472) throw std::invalid_argument("hevc_intra: rdoq in 0..2, rdoq_lam in 0..1472");
     mivc_launch_hevc_intra(B, W, H, P<uint16_t>(sy), P<uint16_t>(su), P<uint16_t>(sv), P<uint16_t>(ry), P<uint16_t>(ru),
                            P<uint16_t>(rv), P<void>(ctu), P<void>(cu), P<int16_t>(cy), P<int16_t>(cu_), P<int16_t>(cv),
                            P<int>(qp), P<int8_t>(run), P<int>(cand), bd, analyze, recon, P<int>(err), sdh,
-                           P<uint8_t>(ctb_mask), S(stream), ctu64);
+                           P<uint8_t>(ctb_mask), S(stream), ctu64, rdoq, rdoq_lam);
   }, py::arg("B"), py::arg("W"), py::arg("H"), py::arg("sy"), py::arg("su"), py::arg("sv"), py::arg("ry"), py::arg("ru"),
      py::arg("rv"), py::arg("ctu"), py::arg("cu"), py::arg("cy"), py::arg("cu_"), py::arg("cv"), py::arg("qp"),
      py::arg("run"), py::arg("cand"), py::arg("bd"), py::arg("analyze"), py::arg("recon"), py::arg("err"),
-     py::arg("stream"), py::arg("sdh") = 0, py::arg("ctb_mask") = 0, py::arg("ctu64") = 0);
+     py::arg("stream"), py::arg("sdh") = 0, py::arg("ctb_mask") = 0, py::arg("ctu64") = 0, py::arg("rdoq") = 0,
+     py::arg("rdoq_lam") = 0);
   m.def("hevc_inter", [](int B, int W, int H, uintptr_t sy, uintptr_t su, uintptr_t sv, uintptr_t fy, uintptr_t fu,
                          uintptr_t fv, uintptr_t ry, uintptr_t ru, uintptr_t rv, uintptr_t ctu, uintptr_t cu, uintptr_t cy,
                          uintptr_t cu_, uintptr_t cv, uintptr_t qp, uintptr_t run, uintptr_t cand, uintptr_t mv,
                          uintptr_t me_cost, int bd, uintptr_t stream, int tu_split, int sdh, int intra_bias,
                          uintptr_t mvb, uintptr_t dirb, uintptr_t f1y, uintptr_t f1u, uintptr_t f1v, uintptr_t wp,
-                         std::vector<uintptr_t> xref, uintptr_t mv8) {
+                         std::vector<uintptr_t> xref, uintptr_t mv8, int rdoq, int rdoq_lam) {
+    if (rdoq < 0 || rdoq > 2 || rdoq_lam < 0 || rdoq_lam > 1472) throw std::invalid_argument("hevc_inter: rdoq in 0..2, rdoq_lam in 0..1472");
     if (dirb && (!mvb || !f1y || !f1u || !f1v)) throw std::invalid_argument("hevc_inter: B motion needs mvb and list-1 planes");
     // xref: (y, u, v) of RefPicList0[1 ..] (x265 --ref), at most 3 pictures
     if (xref.size() % 3 || xref.size() > 9) throw std::invalid_argument("hevc_inter: xref = (y, u, v) x up to 3 pictures");
@@ -626,13 +631,25 @@ PYBIND11_MODULE(_hip, m) {
                            P<int16_t>(cy), P<int16_t>(cu_), P<int16_t>(cv), P<int>(qp), P<int8_t>(run), P<int>(cand),
                            P<int16_t>(mv), P<int>(me_cost), bd, tu_split, sdh, intra_bias, S(stream), P<int16_t>(mvb),
                            P<uint8_t>(dirb), P<uint16_t>(f1y), P<uint16_t>(f1u), P<uint16_t>(f1v), P<int16_t>(wp), xr,
-                           P<int16_t>(mv8));
+                           P<int16_t>(mv8), rdoq, rdoq_lam);
   }, py::arg("B"), py::arg("W"), py::arg("H"), py::arg("sy"), py::arg("su"), py::arg("sv"), py::arg("fy"), py::arg("fu"),
      py::arg("fv"), py::arg("ry"), py::arg("ru"), py::arg("rv"), py::arg("ctu"), py::arg("cu"), py::arg("cy"),
      py::arg("cu_"), py::arg("cv"), py::arg("qp"), py::arg("run"), py::arg("cand"), py::arg("mv"), py::arg("me_cost"),
      py::arg("bd"), py::arg("stream"), py::arg("tu_split") = 0, py::arg("sdh") = 0, py::arg("intra_bias") = 0,
      py::arg("mvb") = 0, py::arg("dirb") = 0, py::arg("f1y") = 0, py::arg("f1u") = 0, py::arg("f1v") = 0,
-     py::arg("wp") = 0, py::arg("xref") = std::vector<uintptr_t>{}, py::arg("mv8") = 0);
+     py::arg("wp") = 0, py::arg("xref") = std::vector<uintptr_t>{}, py::arg("mv8") = 0, py::arg("rdoq") = 0,
+     py::arg("rdoq_lam") = 0);
+  // hv::transform_quant_block on nblk residual blocks [nblk, n, n] (int32): levels (int16), the
+  // reconstructed residual (int32) and the returned flag per block
+  m.def("hevc_tq_probe", [](int nblk, uintptr_t res, uintptr_t lev, uintptr_t rec, uintptr_t flag, int log2n, int bd, int qp,
+                            int intra, int dst, int scan, int sdh, int rdoq, int rdoq_lam, int mfma, uintptr_t stream) {
+    if (mivc_launch_hevc_tq_probe(nblk, P<int>(res), P<int16_t>(lev), P<int>(rec), P<int>(flag), log2n, bd, qp, intra, dst,
+                                  scan, sdh, rdoq, rdoq_lam, mfma, S(stream)) != 0)
+      throw std::invalid_argument("hevc_tq_probe: log2n 2..5, bd 8 / 10, qp 0..51 + 6 (bd - 8), dst at 4x4 only, scan 0..2, "
+                                  "rdoq 0..2, rdoq_lam 0..1472");
+  }, py::arg("nblk"), py::arg("res"), py::arg("lev"), py::arg("rec"), py::arg("flag"), py::arg("log2n"), py::arg("bd"),
+     py::arg("qp"), py::arg("intra"), py::arg("dst"), py::arg("scan"), py::arg("sdh"), py::arg("rdoq"),
+     py::arg("rdoq_lam"), py::arg("mfma"), py::arg("stream"));
   m.def("hevc_b", [](int mode, int B, int wmb, int hmb, uintptr_t src, uintptr_t ref0, uintptr_t ref1, uintptr_t hp0,
                      uintptr_t hp1, uintptr_t mv0, uintptr_t mv1, uintptr_t cost0, uintptr_t cost1, uintptr_t pm0,
                      uintptr_t pm1, uintptr_t tmv, uintptr_t tdir, uintptr_t mvb_in, uintptr_t dir_in, uintptr_t mvb_out,

@@ -8,6 +8,7 @@
 // 8 x 8 tiles), the DCT matrix lives in LDS as int16.
 #pragma once
 #include "kcommon.h"
+#include "hevc_rdoq.h"
 #include "../common/hevc_tables.h"
 
 namespace mivc {
@@ -109,6 +110,9 @@ struct TqParams {
   // 16 / 32-point TUs on the matrix cores (transform_quant_mfma); false: the LDS wave products
   // (the CTB-wavefront intra kernel keeps them: the MFMA form's registers would spill there)
   bool mfma = true;
+  int scan = 0;      // the TU's scanIdx, sign data hiding or not (the RDOQ rate's scan positions)
+  int rdoq = 0;      // x265 --rdoq-level 1 / 2 (hevc_rdoq.h); only the RDOQ instances of the kernels read it
+  int rdoq_lam = 0;  // round(rdoq_lambda * kRdoqLamScale)
 };
 
 // scanIdx of a TU (7.4.9.11): intra luma 4x4 / 8x8 and intra chroma 4x4 follow the mode
@@ -245,10 +249,15 @@ __device__ __forceinline__ bool transform_quant_mfma(const DctLds& D, int* R, in
   return true;
 }
 
+// RDOQ: the instance that can run rate-distortion optimised quantisation (p.rdoq > 0 takes the
+// packed-word path as sign data hiding does, and bypasses the matrix-core form); the default
+// instance holds none of its code
+template <bool RDOQ = false>
 __device__ __forceinline__ bool transform_quant_block(const DctLds& D, int* R, int* S, int16_t* lev, int lstride,
                                                       const TqParams& p) {
   const int n = 1 << p.log2n, lg = p.log2n;
-  if (p.mfma && !p.dst && p.sdh_scan < 0 && (lg == 4 || lg == 5)) {
+  const bool rdoq = RDOQ && p.rdoq > 0;
+  if (p.mfma && !p.dst && p.sdh_scan < 0 && !rdoq && (lg == 4 || lg == 5)) {
     wave_sync();  // R was written by other lanes
     return lg == 5 ? transform_quant_mfma<5>(D, R, lev, lstride, p) : transform_quant_mfma<4>(D, R, lev, lstride, p);
   }
@@ -275,6 +284,10 @@ __device__ __forceinline__ bool transform_quant_block(const DctLds& D, int* R, i
                 const int a = c < 0 ? -c : c;
                 int l = static_cast<int>((static_cast<int64_t>(a) * qscale + qoff) >> qbits);
                 l = l > 32767 ? 32767 : l;
+                if (rdoq) {  // the coefficient itself: rdoq_block chooses the level below
+                  R[v * 32 + u] = c;
+                  return;
+                }
                 if (p.sdh_scan >= 0) {
                   // level, quantisation remainder (HM deltaU) and coefficient sign, packed for
                   // the parity pass below; dequantisation follows it
@@ -294,14 +307,17 @@ __device__ __forceinline__ bool transform_quant_block(const DctLds& D, int* R, i
                 R[v * 32 + u] = static_cast<int>(d < -32768 ? -32768 : (d > 32767 ? 32767 : d));
               });
   wave_sync();
+  if constexpr (RDOQ) {
+    if (rdoq) rdoq_block(R, S, lg, p.scan, p.rdoq, p.rdoq_lam, qscale, qbits);
+  }
+  const int lane = lane_id();
+  auto lvl_at = [&](int x, int y) { return static_cast<int>(static_cast<int16_t>(R[y * 32 + x] & 0xFFFF)); };
   if (p.sdh_scan >= 0) {
     // sign data hiding (7.4.9.11; HM's parity fix): in every 4x4 group whose significant
     // span exceeds 3 scan positions the sum of absolute levels must be odd exactly when the
     // first significant coefficient is negative; otherwise the cheapest +-1 change by the
     // quantisation remainder fixes it.  One lane per group.
     const int nsb = n >> 2, lsb = lg - 2, ngr = nsb * nsb;
-    const int lane = lane_id();
-    auto lvl_at = [&](int x, int y) { return static_cast<int>(static_cast<int16_t>(R[y * 32 + x] & 0xFFFF)); };
     int gi = -1, gnz = 0;
     if (lane < ngr) {
       const int gx = lane % nsb, gy = lane / nsb;
@@ -361,6 +377,8 @@ __device__ __forceinline__ bool transform_quant_block(const DctLds& D, int* R, i
       }
     }
     wave_sync();
+  }
+  if (p.sdh_scan >= 0 || rdoq) {  // the packed words of either pass
     for (int i = lane; i < n * n; i += 64) {  // levels out + dequantisation (8.6.3, flat scaling)
       const int y = i >> lg, x = i & (n - 1);
       const int l = lvl_at(x, y);

@@ -53,6 +53,7 @@ struct HevcInterArgs {
   // 8x8 inter CUs (P pictures, x265's minimum CU): [B, nmb16, 4, 2] per-quadrant vectors of
   // each 16x16 block (p_part8x8 in its HEVC form; all equal = no split); null: 16x16 / 32x32 only
   const int16_t* mv8;
+  int rdoq, rdoq_lam;    // x265 --rdoq-level and its lambda (hevc_rdoq.h); the RDOQ instances read them
 };
 
 // plane c of RefPicList0[r] (constant indices only: no scratch)
@@ -337,8 +338,8 @@ __device__ __forceinline__ void mc_block(SH& S, const uint16_t* ref0, const uint
 }
 
 // TSPLIT: the instance with the residual-quadtree choice (its register footprint stays out of
-// the default instance)
-template <bool TSPLIT>
+// the default instance); RDOQ: the instances with rate-distortion optimised quantisation
+template <bool TSPLIT, bool RDOQ>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 8))) void hevc_inter_cu(HevcInterArgs a) {
   __shared__ typename std::conditional<TSPLIT, InterShared, InterSharedLean>::type S;
   __shared__ hv::DctLds D;
@@ -398,18 +399,26 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 8))) void
     wave_sync();
     const int l2 = c ? lg - 1 : lg;
     const int qc = c ? qpc : qpl;
+    auto tq = [&](int l2t) {  // inter TUs scan diagonally (7.4.9.11)
+      hv::TqParams t{l2t, bd, qc, false, false, a.sdh ? 0 : -1};
+      if constexpr (RDOQ) {
+        t.rdoq = a.rdoq;
+        t.rdoq_lam = a.rdoq_lam;
+      }
+      return t;
+    };
     bool coded = false;
     if constexpr (TSPLIT) {
       if (lg >= 4) {
       coded = c == 0 || split;
       if (c == 0) {
-        const bool nz = hv::transform_quant_block(D, S.R, S.S, lev, pw, hv::TqParams{l2, bd, qc, false, false, a.sdh ? 0 : -1});
+        const bool nz = hv::transform_quant_block<RDOQ>(D, S.R, S.S, lev, pw, tq(l2));
         for (int k = 0; k < 4; ++k) cbfq[k] = nz;
         {
           bool nzq[4];
           for (int k = 0; k < 4; ++k) {
             const int o = (k >> 1) * h * 32 + (k & 1) * h;
-            nzq[k] = hv::transform_quant_block(D, S.R2 + o, S.S, S.lev2 + o, 32, hv::TqParams{l2 - 1, bd, qc, false, false, a.sdh ? 0 : -1});
+            nzq[k] = hv::transform_quant_block<RDOQ>(D, S.R2 + o, S.S, S.lev2 + o, 32, tq(l2 - 1));
           }
           const bool any = nzq[0] || nzq[1] || nzq[2] || nzq[3];
           if (any) {
@@ -435,15 +444,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 8))) void
         const int hc = bs >> 1;
         for (int k = 0; k < 4; ++k) {
           const int o = (k >> 1) * hc * 32 + (k & 1) * hc;
-          const bool nz = hv::transform_quant_block(D, S.R + o, S.S, lev + (k >> 1) * hc * pw + (k & 1) * hc, pw,
-                                                    hv::TqParams{l2 - 1, bd, qc, false, false, a.sdh ? 0 : -1});
+          const bool nz = hv::transform_quant_block<RDOQ>(D, S.R + o, S.S, lev + (k >> 1) * hc * pw + (k & 1) * hc, pw,
+                                                          tq(l2 - 1));
           cbfq[k] |= nz << c;
         }
       }
       }
     }
     if (!coded) {
-      const bool nz = hv::transform_quant_block(D, S.R, S.S, lev, pw, hv::TqParams{l2, bd, qc, false, false, a.sdh ? 0 : -1});
+      const bool nz = hv::transform_quant_block<RDOQ>(D, S.R, S.S, lev, pw, tq(l2));
       for (int k = 0; k < 4; ++k) cbfq[k] |= nz << c;
     }
     // (a block without levels has an all-zero dequantised residual in R)
@@ -476,7 +485,8 @@ extern "C" void mivc_launch_hevc_inter(int B, int W, int H, const uint16_t* sy, 
                                        const int16_t* mv, const int* me_cost, int bd, int tu_split, int sdh,
                                        int intra_bias, void* stream, const int16_t* mvb, const uint8_t* dirb,
                                        const uint16_t* f1y, const uint16_t* f1u, const uint16_t* f1v,
-                                       const int16_t* wp, const uint16_t* const* xref, const int16_t* mv8) {
+                                       const int16_t* wp, const uint16_t* const* xref, const int16_t* mv8, int rdoq,
+                                       int rdoq_lam) {
   HevcInterArgs a;
   a.wp = wp;
   a.mv8 = mv8;
@@ -513,9 +523,17 @@ extern "C" void mivc_launch_hevc_inter(int B, int W, int H, const uint16_t* sy, 
   a.bd = bd;
   a.tu_split = tu_split;
   a.sdh = sdh;
+  a.rdoq = rdoq;
+  a.rdoq_lam = rdoq_lam;
   a.intra_bias = intra_bias;
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(hevc_p_decide, dim3(a.g.nctb(), B), dim3(64), 0, s, a);
-  if (tu_split) hipLaunchKernelGGL(hevc_inter_cu<true>, dim3(a.g.nctb() * 4, B), dim3(64), 0, s, a);
-  else hipLaunchKernelGGL(hevc_inter_cu<false>, dim3(a.g.nctb() * 4, B), dim3(64), 0, s, a);
+  const dim3 grid(a.g.nctb() * 4, B);
+  if (rdoq) {
+    if (tu_split) hipLaunchKernelGGL((hevc_inter_cu<true, true>), grid, dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((hevc_inter_cu<false, true>), grid, dim3(64), 0, s, a);
+  } else {
+    if (tu_split) hipLaunchKernelGGL((hevc_inter_cu<true, false>), grid, dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((hevc_inter_cu<false, false>), grid, dim3(64), 0, s, a);
+  }
 }

@@ -35,6 +35,7 @@ struct HevcIntraArgs {
   int bd;
   int* err;
   int sdh;                                // sign data hiding in the quantiser
+  int rdoq, rdoq_lam;                     // x265 --rdoq-level and its lambda (hevc_rdoq.h); hevc_intra_recon<true> reads them
   int nxn_in_p;                           // evaluate PART_NxN in P pictures too
   const uint8_t* ctb_mask;                // [B, nctb] analyse only where nonzero (P pictures: the CTBs
                                           // where intra may beat the motion search); null = every CTB
@@ -511,7 +512,7 @@ struct ReconShared {
 };
 
 // reconstruct one CU component: refs from the LDS tile, predict, transform/quantise, store
-template <bool LUMA>
+template <bool LUMA, bool RDOQ>
 __device__ __forceinline__ bool recon_block(const HevcIntraArgs& a, ReconShared& S, const hv::DctLds& D, int slot,
                                             int comp, int rx, int ry, int cx, int cy, int log2n, int mode, int zc, int qpp,
                                             bool dst = false) {
@@ -560,7 +561,12 @@ __device__ __forceinline__ bool recon_block(const HevcIntraArgs& a, ReconShared&
                  static_cast<size_t>(Y0) * pw + X0;
   hv::TqParams tp{log2n, bd, qpp, true, dst, a.sdh ? hv::tu_scan_idx(true, LUMA, log2n, mode) : -1};
   tp.mfma = false;
-  const bool nz = hv::transform_quant_block(D, S.R, S.S, lev, pw, tp);
+  if constexpr (RDOQ) {
+    tp.scan = hv::tu_scan_idx(true, LUMA, log2n, mode);
+    tp.rdoq = a.rdoq;
+    tp.rdoq_lam = a.rdoq_lam;
+  }
+  const bool nz = hv::transform_quant_block<RDOQ>(D, S.R, S.S, lev, pw, tp);
   uint16_t* rec = (LUMA ? a.rec_y : (comp == 1 ? a.rec_u : a.rec_v)) + slot * (LUMA ? g.ysize() : g.csize());
   for (int i = lane; i < n * n; i += 64) {
     const int x = i & (n - 1), y = i >> log2n;
@@ -577,6 +583,7 @@ __device__ __forceinline__ bool recon_block(const HevcIntraArgs& a, ReconShared&
 // One colour component per workgroup (comp = blockIdx.y): the three planes of a picture are
 // independent intra wavefronts (no cross-component prediction in Main / Main 10), so a slot's
 // luma, Cb and Cr run side by side on three CUs instead of one after another in one wave.
+template <bool RDOQ>
 __device__ __forceinline__ void hevc_recon_ctb(const HevcIntraArgs& a, ReconShared& S, const hv::DctLds& D, int slot,
                                                int rx, int ry, int run, int comp) {
   const HevcGeom& g = a.g;
@@ -636,15 +643,15 @@ __device__ __forceinline__ void hevc_recon_ctb(const HevcIntraArgs& a, ReconShar
       const int cx = gx * 8, cy = gy * 8;
       bool nz = false;
       if (!luma) {
-        nz = recon_block<false>(a, S, D, slot, comp, rx, ry, cx / 2, cy / 2, log2n - 1, mode, 4 * k, qpc);
+        nz = recon_block<false, RDOQ>(a, S, D, slot, comp, rx, ry, cx / 2, cy / 2, log2n - 1, mode, 4 * k, qpc);
       } else if (log2n == 3 && (__builtin_amdgcn_readfirstlane(cu->flags) & 8)) {
         // PART_NxN: four 4x4 luma PUs in z-order, DST, each predicted from the previous ones
         const uint32_t pm = __builtin_amdgcn_readfirstlane(*reinterpret_cast<const uint32_t*>(cu->mv));
         for (int j = 0; j < 4; ++j)
-          nz |= recon_block<true>(a, S, D, slot, 0, rx, ry, cx + (j & 1) * 4, cy + (j >> 1) * 4, 2,
+          nz |= recon_block<true, RDOQ>(a, S, D, slot, 0, rx, ry, cx + (j & 1) * 4, cy + (j >> 1) * 4, 2,
                                   static_cast<int>((pm >> (8 * j)) & 255u), 4 * k + j, qpl, true);
       } else {
-        nz = recon_block<true>(a, S, D, slot, 0, rx, ry, cx, cy, log2n, mode, 4 * k, qpl);
+        nz = recon_block<true, RDOQ>(a, S, D, slot, 0, rx, ry, cx, cy, log2n, mode, 4 * k, qpl);
       }
       if (lane < step) {
         // cbf bit `comp` of the granule's record (byte 2 of its first word): the three
@@ -676,6 +683,8 @@ __device__ __forceinline__ void hevc_recon_ctb(const HevcIntraArgs& a, ReconShar
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
+// RDOQ: the instance with rate-distortion optimised quantisation (kept out of the default one)
+template <bool RDOQ>
 __global__ __launch_bounds__(64 * kHevcIntraWaves) void hevc_intra_recon(HevcIntraArgs a) {
   __shared__ ReconShared SS[kHevcIntraWaves];
   __shared__ hv::DctLds D;
@@ -709,7 +718,7 @@ __global__ __launch_bounds__(64 * kHevcIntraWaves) void hevc_intra_recon(HevcInt
         for (int q = 0; q < nq; ++q) {
           const int bx = (x << c64) + (q & 1), by = (y << c64) + (q >> 1);
           if (bx >= g.wctb || by >= g.hctb) continue;
-          hevc_recon_ctb(a, S, D, slot, bx, by, run, comp);
+          hevc_recon_ctb<RDOQ>(a, S, D, slot, bx, by, run, comp);
         }
         row_publish(prog, y, x + 1);
       }
@@ -738,7 +747,7 @@ __global__ __launch_bounds__(64 * kHevcIntraWaves) void hevc_intra_recon(HevcInt
           const int bx = (x << c64) + (q & 1), by = (y << c64) + (q >> 1);
           if (bx >= g.wctb || by >= g.hctb) continue;
           if (block_work(bx, by)) {
-            hevc_recon_ctb(a, S, D, slot, bx, by, run, comp);
+            hevc_recon_ctb<RDOQ>(a, S, D, slot, bx, by, run, comp);
           } else {
             if (lane_id() == 0) S.saved_x = -2;
             wave_sync();
@@ -779,6 +788,8 @@ static HevcIntraArgs make_intra_args(int B, int W, int H, const uint16_t* sy, co
   a.bd = bd;
   a.err = err;
   a.sdh = sdh;
+  a.rdoq = 0;
+  a.rdoq_lam = 0;
   a.nxn_in_p = 0;
   a.ctb_mask = nullptr;
   a.ctu64 = 0;
@@ -789,11 +800,14 @@ extern "C" void mivc_launch_hevc_intra(int B, int W, int H, const uint16_t* sy, 
                                        uint16_t* ry, uint16_t* ru, uint16_t* rv, void* ctu, void* cu, int16_t* cy,
                                        int16_t* cu_, int16_t* cv, const int* qp, const int8_t* run, int* cand, int bd,
                                        int analyze, int recon, int* err, int sdh, const uint8_t* ctb_mask,
-                                       void* stream, int ctu64) {
+                                       void* stream, int ctu64, int rdoq, int rdoq_lam) {
   HevcIntraArgs a = make_intra_args(B, W, H, sy, su, sv, ry, ru, rv, ctu, cu, cy, cu_, cv, qp, run, cand, bd, err, sdh);
   a.ctb_mask = ctb_mask;
   a.ctu64 = ctu64;
+  a.rdoq = rdoq;
+  a.rdoq_lam = rdoq_lam;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (analyze) hipLaunchKernelGGL(hevc_intra_analyze, dim3(a.g.nctb(), B), dim3(256), 0, s, a);
-  if (recon) hipLaunchKernelGGL(hevc_intra_recon, dim3(B, 3), dim3(64 * kHevcIntraWaves), 0, s, a);
+  if (recon && rdoq) hipLaunchKernelGGL(hevc_intra_recon<true>, dim3(B, 3), dim3(64 * kHevcIntraWaves), 0, s, a);
+  else if (recon) hipLaunchKernelGGL(hevc_intra_recon<false>, dim3(B, 3), dim3(64 * kHevcIntraWaves), 0, s, a);
 }

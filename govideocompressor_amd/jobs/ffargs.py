@@ -245,6 +245,7 @@ HEVC_PARAMS = {
     "max-merge": ("max_merge", _int_in(1, 5)),
     "signhide": ("sdh", _flag),
     "no-signhide": ("sdh", lambda v: not _flag(v)),
+    "rdoq-level": ("rdoq_level", _int_in(0, 2)),
     "tu-inter-depth": ("tu_inter_depth", lambda v: _int_in(1, 2)(v) - 1),
     "scenecut": ("scenecut", _int_in(0, 100)),
     "rc-lookahead": ("lookahead", lambda v: int(v) > 0),

@@ -74,6 +74,8 @@ HEVC = {
     "MIVC_HEVC_INTER8_OVERHEAD": "inter8_overhead",
     "MIVC_HEVC_TU_INTER_DEPTH": "tu_inter_depth",
     "MIVC_HEVC_SDH": "sdh",
+    "MIVC_HEVC_RDOQ": "rdoq_level",
+    "MIVC_HEVC_RDOQ_LAMBDA": "rdoq_lambda",
     "MIVC_HEVC_AQ_MODE": "aq_mode",
 }
 # bench.py shape knobs (they change what is measured, so they also need --allow-knobs)

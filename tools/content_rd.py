@@ -97,6 +97,16 @@ CONFIGS = {
 HEVC_CONFIGS = {
     "default": dict(),
     "signhide": dict(sdh=True),
+    # x265 --rdoq-level: rate-distortion optimised quantisation and its lambda multiplier (rdoq1 /
+    # rdoq2 at the derived lambda, 1.0)
+    "rdoq1": dict(rdoq_level=1, rdoq_lambda=1.0),
+    "rdoq2": dict(rdoq_level=2, rdoq_lambda=1.0),
+    "rdoq1l050": dict(rdoq_level=1, rdoq_lambda=0.5),
+    "rdoq2l025": dict(rdoq_level=2, rdoq_lambda=0.25),
+    "rdoq2l035": dict(rdoq_level=2, rdoq_lambda=0.35),
+    "rdoq2l050": dict(rdoq_level=2, rdoq_lambda=0.5),
+    "rdoq2l075": dict(rdoq_level=2, rdoq_lambda=0.75),
+    "rdoq2l150": dict(rdoq_level=2, rdoq_lambda=1.5),
     "bf0": dict(bframes=0),
     "bf3": dict(bframes=3, b_qp_offset=2),
     "bqp2": dict(b_qp_offset=2),
