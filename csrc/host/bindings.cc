@@ -368,6 +368,7 @@ hevc::HevcConfig hevc_cfg_from(const py::dict& d) {
   c.pyramid = dget<int>(d, "pyramid", 0);
   c.ctu64 = dget<int>(d, "ctu64", 0);
   c.weightp = dget<int>(d, "weightp", 0);
+  c.weightb = dget<int>(d, "weightb", 0);
   c.refs = dget<int>(d, "refs", 1);
   if (c.refs < 1 || c.refs > hevc::kMaxRefs) throw std::runtime_error("HEVC: refs in 1..4");
   if (c.tu_inter_depth < 0 || c.tu_inter_depth > 1) throw std::runtime_error("HEVC: tu_inter_depth in 0..1");
@@ -577,15 +578,19 @@ hevc::HevcFrameParams hevc_frame_from(const py::dict& fp, std::vector<py::array>
       f.rps_used[i] = static_cast<uint8_t>(e[1].cast<int>() ? 1 : 0);
     }
   }
-  if (fp.contains("wp") && !fp["wp"].is_none()) {  // [w_y, o_y, w_cb, o_cb, w_cr, o_cr]
-    const py::list l = fp["wp"].cast<py::list>();
-    if (l.size() != 6) throw std::runtime_error("wp: 6 entries (weight, offset per component)");
-    f.wp = 1;
+  for (int x = 0; x < 2; ++x) {  // "wp" / "wp1" (list 1, B slices): [w_y, o_y, w_cb, o_cb, w_cr, o_cr]
+    const char* key = x ? "wp1" : "wp";
+    if (!fp.contains(key) || fp[key].is_none()) continue;
+    const py::list l = fp[key].cast<py::list>();
+    if (l.size() != 6) throw std::runtime_error(std::string(key) + ": 6 entries (weight, offset per component)");
+    (x ? f.wp1 : f.wp) = 1;
+    int* w = x ? f.wp1_w : f.wp_w;
+    int* o = x ? f.wp1_o : f.wp_o;
     for (int c = 0; c < 3; ++c) {
-      f.wp_w[c] = l[2 * c].cast<int>();
-      f.wp_o[c] = l[2 * c + 1].cast<int>();
-      if (f.wp_w[c] < -64 || f.wp_w[c] > 191 || f.wp_o[c] < -128 || f.wp_o[c] > 127)
-        throw std::runtime_error("wp: weight in -64..191, offset in -128..127");
+      w[c] = l[2 * c].cast<int>();
+      o[c] = l[2 * c + 1].cast<int>();
+      if (w[c] < -64 || w[c] > 191 || o[c] < -128 || o[c] > 127)
+        throw std::runtime_error(std::string(key) + ": weight in -64..191, offset in -128..127");
     }
   }
   if (fp.contains("col_poc")) {

@@ -46,6 +46,9 @@ struct HevcConfig {
   // weighted_pred_flag (x265 --weightp): P slices carry pred_weight_table() with log2
   // denominators 6 (luma and chroma) and the picture's FrameParams::wp weights
   int weightp = 0;
+  // weighted_bipred_flag (x265 --weightb): every B slice carries pred_weight_table() with log2
+  // denominators 6 and the picture's FrameParams::wp (list 0) / wp1 (list 1) weights
+  int weightb = 0;
   // x265 --ref: the most active list-0 pictures of a P slice (HevcFrameParams::num_ref); sizes
   // the DPB (sps_max_dec_pic_buffering)
   int refs = 1;
@@ -97,6 +100,11 @@ struct HevcFrameParams {
   int wp = 0;
   int wp_w[3] = {64, 64, 64};
   int wp_o[3] = {0, 0, 0};
+  // with HevcConfig::weightb, B slices: wp weights RefPicList0[0] and wp1 RefPicList1[0] in the
+  // same form (either may be 0: that list's flags off)
+  int wp1 = 0;
+  int wp1_w[3] = {64, 64, 64};
+  int wp1_o[3] = {0, 0, 0};
 };
 
 struct HevcSliceStats {

@@ -181,7 +181,7 @@ std::vector<uint8_t> hevc_parameter_sets(const HevcConfig& c) {
     bw.put_se(0);   // pps_cr_qp_offset
     bw.put_bit(0);  // pps_slice_chroma_qp_offsets_present_flag
     bw.put_bit(c.weightp ? 1 : 0);  // weighted_pred_flag
-    bw.put_bit(0);  // weighted_bipred_flag
+    bw.put_bit(c.weightb ? 1 : 0);  // weighted_bipred_flag
     bw.put_bit(0);  // transquant_bypass_enabled_flag
     bw.put_bit(0);  // tiles_enabled_flag
     bw.put_bit(c.wpp ? 1 : 0);  // entropy_coding_sync_enabled_flag
@@ -215,6 +215,8 @@ void slice_header(BitWriter& bw, const HevcConfig& c, const HevcFrameParams& fp)
   const bool inter = fp.slice_type != 2, bslice = fp.slice_type == 0;
   if (bslice && fp.ref_poc[1] < 0) throw std::runtime_error("HEVC: a B slice needs ref_poc[1]");
   if (inter && c.tmvp && !fp.col.set) throw std::runtime_error("HEVC: TMVP needs the collocated picture's records");
+  if (fp.wp1 && !bslice) throw std::runtime_error("HEVC: wp1 (list-1 weights) belongs to B slices");
+  if (bslice && !c.weightb && (fp.wp || fp.wp1)) throw std::runtime_error("HEVC: weights in a B slice need HevcConfig::weightb");
   if (!idr) {
     bw.put(fp.poc & 255, 8);  // slice_pic_order_cnt_lsb
     const int r0 = fp.ref_poc[0] >= 0 ? fp.ref_poc[0] : fp.poc - 1;
@@ -312,6 +314,25 @@ void slice_header(BitWriter& bw, const HevcConfig& c, const HevcFrameParams& fp)
         for (int j = 1; j < 3; ++j) {
           bw.put_se(fp.wp_w[j] - 64);  // delta_chroma_weight_l0
           bw.put_se(fp.wp_o[j] - 128 + ((128 * fp.wp_w[j]) >> 6));  // delta_chroma_offset_l0
+        }
+      }
+    } else if (c.weightb && bslice) {
+      // every B slice of a weighted_bipred stream carries the table: the list-0 entries, then
+      // the list-1 entries (RefPicListX[0] only; the two lists hold different pictures here)
+      bw.put_ue(6);                 // luma_log2_weight_denom
+      bw.put_se(0);                 // delta_chroma_log2_weight_denom
+      for (int l = 0; l < 2; ++l) {
+        const int on = l ? fp.wp1 : fp.wp, nl = l ? n1 : n0;
+        const int* w = l ? fp.wp1_w : fp.wp_w;
+        const int* o = l ? fp.wp1_o : fp.wp_o;
+        for (int i = 0; i < nl; ++i) bw.put_bit(i == 0 && on ? 1 : 0);  // luma_weight_lX_flag[i]
+        for (int i = 0; i < nl; ++i) bw.put_bit(i == 0 && on ? 1 : 0);  // chroma_weight_lX_flag[i]
+        if (!on) continue;
+        bw.put_se(w[0] - 64);  // delta_luma_weight_lX
+        bw.put_se(o[0]);       // luma_offset_lX
+        for (int j = 1; j < 3; ++j) {
+          bw.put_se(w[j] - 64);  // delta_chroma_weight_lX
+          bw.put_se(o[j] - 128 + ((128 * w[j]) >> 6));  // delta_chroma_offset_lX
         }
       }
     }

@@ -142,7 +142,12 @@ void mivc_launch_hevc_inter(int B, int W, int H, const uint16_t* sy, const uint1
                             const int8_t* run, const int* cand, const int16_t* mv, const int* me_cost, int bd,
                             int tu_split, int sdh, int intra_bias, void* stream, const int16_t* mvb,
                             const uint8_t* dirb, const uint16_t* f1y, const uint16_t* f1u, const uint16_t* f1v,
-                            const int16_t* wp, const uint16_t* const* xref, const int16_t* mv8, int rdoq, int rdoq_lam);
+                            const int16_t* wp, const uint16_t* const* xref, const int16_t* mv8, int rdoq, int rdoq_lam,
+                            const int16_t* wpb);
+int mivc_launch_hevc_mc_probe(int ncase, const uint16_t* ref0, const uint16_t* ref1, int pw, int ph, const int16_t* cases,
+                              uint16_t* out, int nt, int n, int dir, int bd, int ww, int wo, int ww1, int wo1, int wb,
+                              int lean, void* stream);
+int mivc_launch_wp_ref8(const uint8_t* ref, uint8_t* dst, const int* wt, int B, long long plane_bytes, void* stream);
 int mivc_launch_hevc_tq_probe(int nblk, const int* res, int16_t* lev, int* rec, int* flag, int log2n, int bd, int qp,
                               int intra, int dst, int scan, int sdh, int rdoq, int rdoq_lam, int mfma, void* stream);
 void mivc_launch_hevc_b(int mode, int B, int wmb, int hmb, const uint8_t* src_y, const uint8_t* ref0, const uint8_t* ref1,
@@ -619,7 +624,9 @@ PYBIND11_MODULE(_hip, m) {
                          uintptr_t cu_, uintptr_t cv, uintptr_t qp, uintptr_t run, uintptr_t cand, uintptr_t mv,
                          uintptr_t me_cost, int bd, uintptr_t stream, int tu_split, int sdh, int intra_bias,
                          uintptr_t mvb, uintptr_t dirb, uintptr_t f1y, uintptr_t f1u, uintptr_t f1v, uintptr_t wp,
-                         std::vector<uintptr_t> xref, uintptr_t mv8, int rdoq, int rdoq_lam) {
+                         std::vector<uintptr_t> xref, uintptr_t mv8, int rdoq, int rdoq_lam, uintptr_t wpb) {
+    // wpb: x265 --weightb, int16 [B][2][6] list-0 / list-1 weights of a B picture
+    if (wpb && (!dirb || wp || !xref.empty())) throw std::invalid_argument("hevc_inter: wpb belongs to B pictures (dirb, no wp / xref)");
     if (rdoq < 0 || rdoq > 2 || rdoq_lam < 0 || rdoq_lam > 1472) throw std::invalid_argument("hevc_inter: rdoq in 0..2, rdoq_lam in 0..1472");
     if (dirb && (!mvb || !f1y || !f1u || !f1v)) throw std::invalid_argument("hevc_inter: B motion needs mvb and list-1 planes");
     // xref: (y, u, v) of RefPicList0[1 ..] (x265 --ref), at most 3 pictures
@@ -631,14 +638,30 @@ PYBIND11_MODULE(_hip, m) {
                            P<int16_t>(cy), P<int16_t>(cu_), P<int16_t>(cv), P<int>(qp), P<int8_t>(run), P<int>(cand),
                            P<int16_t>(mv), P<int>(me_cost), bd, tu_split, sdh, intra_bias, S(stream), P<int16_t>(mvb),
                            P<uint8_t>(dirb), P<uint16_t>(f1y), P<uint16_t>(f1u), P<uint16_t>(f1v), P<int16_t>(wp), xr,
-                           P<int16_t>(mv8), rdoq, rdoq_lam);
+                           P<int16_t>(mv8), rdoq, rdoq_lam, P<int16_t>(wpb));
   }, py::arg("B"), py::arg("W"), py::arg("H"), py::arg("sy"), py::arg("su"), py::arg("sv"), py::arg("fy"), py::arg("fu"),
      py::arg("fv"), py::arg("ry"), py::arg("ru"), py::arg("rv"), py::arg("ctu"), py::arg("cu"), py::arg("cy"),
      py::arg("cu_"), py::arg("cv"), py::arg("qp"), py::arg("run"), py::arg("cand"), py::arg("mv"), py::arg("me_cost"),
      py::arg("bd"), py::arg("stream"), py::arg("tu_split") = 0, py::arg("sdh") = 0, py::arg("intra_bias") = 0,
      py::arg("mvb") = 0, py::arg("dirb") = 0, py::arg("f1y") = 0, py::arg("f1u") = 0, py::arg("f1v") = 0,
      py::arg("wp") = 0, py::arg("xref") = std::vector<uintptr_t>{}, py::arg("mv8") = 0, py::arg("rdoq") = 0,
-     py::arg("rdoq_lam") = 0);
+     py::arg("rdoq_lam") = 0, py::arg("wpb") = 0);
+  // mc_block (hevc_mc.h) on ncase blocks of planted reference planes [ph, pw] (uint16): cases
+  // int16 [ncase, 6] = block x, y, list-0 vector, list-1 vector; out uint16 [ncase, n * n]
+  m.def("hevc_mc_probe", [](int ncase, uintptr_t ref0, uintptr_t ref1, int pw, int ph, uintptr_t cases, uintptr_t out, int nt,
+                            int n, int dir, int bd, int ww, int wo, int ww1, int wo1, int wb, int lean, uintptr_t stream) {
+    if (mivc_launch_hevc_mc_probe(ncase, P<uint16_t>(ref0), P<uint16_t>(ref1), pw, ph, P<int16_t>(cases), P<uint16_t>(out), nt,
+                                  n, dir, bd, ww, wo, ww1, wo1, wb, lean, S(stream)) != 0)
+      throw std::invalid_argument("hevc_mc_probe: nt 8 with n 8 / 16 / 32 or nt 4 with n 4 / 8 / 16, dir 1..3, bd 8 / 10, "
+                                  "weights 0..127, offsets -128..127, list-1 weights only with wb");
+  }, py::arg("ncase"), py::arg("ref0"), py::arg("ref1"), py::arg("pw"), py::arg("ph"), py::arg("cases"), py::arg("out"),
+     py::arg("nt"), py::arg("n"), py::arg("dir"), py::arg("bd"), py::arg("ww"), py::arg("wo"), py::arg("ww1"), py::arg("wo1"),
+     py::arg("wb"), py::arg("lean"), py::arg("stream"));
+  // forward-weighted 8-bit reference proxies of a weighted B step: wt int32 [B, 2] = (w, o) over 2^6
+  m.def("wp_ref8", [](uintptr_t ref, uintptr_t dst, uintptr_t wt, int B, long long plane_bytes, uintptr_t stream) {
+    if (mivc_launch_wp_ref8(P<uint8_t>(ref), P<uint8_t>(dst), P<int>(wt), B, plane_bytes, S(stream)) != 0)
+      throw std::invalid_argument("wp_ref8: B >= 1 and a plane size that is a positive multiple of 4");
+  });
   // hv::transform_quant_block on nblk residual blocks [nblk, n, n] (int32): levels (int16), the
   // reconstructed residual (int32) and the returned flag per block
   m.def("hevc_tq_probe", [](int nblk, uintptr_t res, uintptr_t lev, uintptr_t rec, uintptr_t flag, int log2n, int bd, int qp,

@@ -15,6 +15,7 @@
 //   inter rounding offset, reconstruction.  No dependency between CUs: fully
 //   parallel; the intra CUs of the picture are then coded by hevc_intra_recon.
 #include "hevc_common.h"
+#include "hevc_mc.h"
 
 namespace mivc {
 namespace gpu {
@@ -46,6 +47,10 @@ struct HevcInterArgs {
   // log2 denominators kWpLog2 for luma and chroma): [B][6] = weight, offset (8-bit units) of
   // Y, Cb, Cr; weight 0 = the slot's picture is not weighted.  Null: default weighting.
   const int16_t* wp;
+  // x265 --weightb (the WB instances; B pictures): [B][2][6], the same rows for RefPicList0[0] and
+  // RefPicList1[0]; a slot with a weight on either list predicts every CU by the explicit
+  // formulas, a list without weight entering as (64, 0)
+  const int16_t* wpb;
   // x265 --ref: RefPicList0[1 ..] reconstructions of a P picture (a motion's direction byte in
   // dirb carries its list-0 refIdx in bits 2-3; the CU records take it in pad[0]); explicit
   // weights apply to RefPicList0[0] only
@@ -61,8 +66,6 @@ __device__ __forceinline__ const uint16_t* l0_plane(const HevcInterArgs& a, int 
   const uint16_t* const* x = c == 0 ? a.xref_y : (c == 1 ? a.xref_u : a.xref_v);
   return r == 0 ? (c == 0 ? a.ref_y : (c == 1 ? a.ref_u : a.ref_v)) : (r == 1 ? x[0] : (r == 2 ? x[1] : x[2]));
 }
-
-constexpr int kWpLog2 = 6;
 
 __device__ __forceinline__ int lambda_satd_i(int qp, int bd) {
   return static_cast<int>(0.755f * exp2f((qp - 12) / 6.0f) * static_cast<float>(1 << (bd - 8)) + 0.5f);
@@ -183,41 +186,6 @@ __global__ __launch_bounds__(64) void hevc_p_decide(HevcInterArgs a) {
   }
 }
 
-// ============================================================== inter reconstruction
-constexpr int kLumaTapsD[4][8] = {{0, 0, 0, 64, 0, 0, 0, 0},
-                                  {-1, 4, -10, 58, 17, -5, 1, 0},
-                                  {-1, 4, -11, 40, 40, -11, 4, -1},
-                                  {0, 1, -5, 17, 58, -10, 4, -1}};
-constexpr int kChromaTapsD[8][4] = {{0, 64, 0, 0},    {-2, 58, 10, -2}, {-4, 54, 16, -2}, {-6, 46, 28, -4},
-                                    {-4, 36, 36, -4}, {-4, 28, 46, -6}, {-2, 16, 54, -4}, {-2, 10, 58, -2}};
-
-struct InterShared {
-  uint16_t win[39 * 39];  // reference window (n + 7)^2
-  int tmp[39 * 32];       // horizontal pass
-  int R[32 * 32], S[32 * 32];
-  int R2[32 * 32];        // luma residual / reconstruction of the quarter-TU alternative
-  int16_t lev2[32 * 32];  // its levels
-  uint16_t pred[32 * 32];
-};
-
-// The default instance's LDS (15.8 KB with the DCT matrix instead of 26.5 KB: 10 workgroups
-// per CU instead of 6): the motion-compensation window and horizontal pass live only until
-// the residual is formed, the transform scratch S only after, so they share storage; the
-// 16-bit intermediates (horizontal pass, the list-0 prediction of bi-prediction) are what
-// the standard bounds them to (8.5.3.3.3: 14-bit predSamples, 16-bit first stage)
-struct InterSharedLean {
-  union {
-    struct {
-      uint16_t win[39 * 39];
-      int16_t tmp[39 * 32];
-    };
-    int S[32 * 32];
-  };
-  int R[32 * 32];
-  int16_t R2[32 * 32];  // list-0 prediction samples of a bi-predicted block
-  uint16_t pred[32 * 32];
-};
-
 // rate proxy of a block's levels (bits): ~3 + 2 log2|l| per non-zero level (wave reduction)
 __device__ __forceinline__ int level_bits(const int16_t* lev, int stride, int n) {
   int b = 0;
@@ -245,101 +213,11 @@ __device__ __forceinline__ long long recon_ssd(const SH& S, const int* R, const 
   return (static_cast<long long>(sum64(hi)) << 30) + sum64(lo);
 }
 
-// motion-compensated prediction samples predSamplesLX (14-bit intermediate, 8.5.3.3.3
-// fractional interpolation) of one n x n block of a component into dst[y * n + x]
-template <int NT, typename SH, typename DT>
-__device__ __forceinline__ void mc_inter(SH& S, const uint16_t* ref, int pw, int ph, int bx, int by, int n,
-                                         int mvx, int mvy, int bd, DT* dst) {
-  const int lane = lane_id();
-  const int fb = NT == 8 ? 2 : 3;  // fraction bits
-  const int half = NT / 2 - 1;     // taps before the sample
-  const int fx = mvx & ((1 << fb) - 1), fy = mvy & ((1 << fb) - 1);
-  const int ix = bx + (mvx >> fb) - half, iy = by + (mvy >> fb) - half;
-  const int wn = n + NT - 1;
-  for (int i = lane; i < wn * wn; i += 64) {
-    const int r = i / wn, c = i - r * wn;
-    const int x = clampi(ix + c, 0, pw - 1), y = clampi(iy + r, 0, ph - 1);
-    S.win[r * wn + c] = ref[static_cast<size_t>(y) * pw + x];
-  }
-  wave_sync();
-  const int sh1 = bd - 8 < 4 ? bd - 8 : 4;
-  const int wsh = 14 - bd;
-  auto tap = [&](int f, int k) { return NT == 8 ? kLumaTapsD[f][k] : kChromaTapsD[f][k]; };
-  if (fx != 0 && fy != 0) {  // separable: horizontal pass over n + NT - 1 rows
-    for (int i = lane; i < wn * n; i += 64) {
-      const int r = i / n, x = i - r * n;
-      int s = 0;
-#pragma unroll
-      for (int k = 0; k < NT; ++k) s += tap(fx, k) * S.win[r * wn + x + k];
-      S.tmp[r * 32 + x] = static_cast<std::remove_reference_t<decltype(S.tmp[0])>>(s >> sh1);
-    }
-    wave_sync();
-  }
-  for (int i = lane; i < n * n; i += 64) {
-    const int y = i / n, x = i - y * n;
-    int v;
-    if (fx == 0 && fy == 0) {
-      v = static_cast<int>(S.win[(y + half) * wn + x + half]) << wsh;
-    } else if (fy == 0) {
-      int s = 0;
-#pragma unroll
-      for (int k = 0; k < NT; ++k) s += tap(fx, k) * S.win[(y + half) * wn + x + k];
-      v = s >> sh1;
-    } else if (fx == 0) {
-      int s = 0;
-#pragma unroll
-      for (int k = 0; k < NT; ++k) s += tap(fy, k) * S.win[(y + k) * wn + x + half];
-      v = s >> sh1;
-    } else {
-      int s = 0;
-#pragma unroll
-      for (int k = 0; k < NT; ++k) s += tap(fy, k) * S.tmp[(y + k) * 32 + x];
-      v = s >> 6;
-    }
-    dst[i] = static_cast<DT>(v);
-  }
-  wave_sync();
-}
-
-// prediction of one n x n block of a component into S.pred: default weighted sample
-// prediction (8.5.3.3.4.2) of one list, or the average of both (bi-prediction)
-template <int NT, typename SH>
-__device__ __forceinline__ void mc_block(SH& S, const uint16_t* ref0, const uint16_t* ref1, int pw, int ph,
-                                         int bx, int by, int n, int dir, int mvx, int mvy, int mv1x, int mv1y, int bd,
-                                         int ww = 0, int wo = 0) {
-  const int lane = lane_id();
-  const int maxv = (1 << bd) - 1;
-  if (dir == hevc::DIR_BI) {
-    mc_inter<NT>(S, ref0, pw, ph, bx, by, n, mvx, mvy, bd, S.R2);
-    mc_inter<NT>(S, ref1, pw, ph, bx, by, n, mv1x, mv1y, bd, S.R);
-    const int sh2 = 15 - bd, off2 = 1 << (sh2 - 1);
-    for (int i = lane; i < n * n; i += 64) {
-      const int v = (S.R2[i] + S.R[i] + off2) >> sh2;
-      S.pred[i] = static_cast<uint16_t>(v < 0 ? 0 : (v > maxv ? maxv : v));
-    }
-  } else {
-    const bool l1 = dir == hevc::DIR_L1;
-    mc_inter<NT>(S, l1 ? ref1 : ref0, pw, ph, bx, by, n, l1 ? mv1x : mvx, l1 ? mv1y : mvy, bd, S.R);
-    if (ww) {  // explicit weighted sample prediction, uni-directional (8.5.3.3.4.3)
-      const int lwd = kWpLog2 + 14 - bd, rnd = 1 << (lwd - 1), o = wo * (1 << (bd - 8));
-      for (int i = lane; i < n * n; i += 64) {
-        const int v = ((S.R[i] * ww + rnd) >> lwd) + o;
-        S.pred[i] = static_cast<uint16_t>(v < 0 ? 0 : (v > maxv ? maxv : v));
-      }
-    } else {
-      const int wsh = 14 - bd, woff = 1 << (wsh - 1);
-      for (int i = lane; i < n * n; i += 64) {
-        const int v = (S.R[i] + woff) >> wsh;
-        S.pred[i] = static_cast<uint16_t>(v < 0 ? 0 : (v > maxv ? maxv : v));
-      }
-    }
-  }
-  wave_sync();
-}
 
 // TSPLIT: the instance with the residual-quadtree choice (its register footprint stays out of
-// the default instance); RDOQ: the instances with rate-distortion optimised quantisation
-template <bool TSPLIT, bool RDOQ>
+// the default instance); RDOQ: the instances with rate-distortion optimised quantisation; WB: the
+// instances of B pictures with explicit weights (x265 --weightb)
+template <bool TSPLIT, bool RDOQ, bool WB>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 8))) void hevc_inter_cu(HevcInterArgs a) {
   __shared__ typename std::conditional<TSPLIT, InterShared, InterSharedLean>::type S;
   __shared__ hv::DctLds D;
@@ -386,10 +264,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 8))) void
     const uint16_t* src = (c == 0 ? a.src_y : (c == 1 ? a.src_u : a.src_v)) + slot * ps;
     uint16_t* rec = (c == 0 ? a.rec_y : (c == 1 ? a.rec_u : a.rec_v)) + slot * ps;
     int16_t* lev = (c == 0 ? a.coef_y : (c == 1 ? a.coef_u : a.coef_v)) + slot * ps + static_cast<size_t>(by) * pw + bx;
-    const int ww = (a.wp && dir == hevc::DIR_L0 && r0 == 0) ? a.wp[slot * 6 + 2 * c] : 0;
-    const int wo = ww ? a.wp[slot * 6 + 2 * c + 1] : 0;
-    if (c == 0) mc_block<8>(S, ref, ref1, pw, ph, bx, by, bs, dir, mvx, mvy, mv1x, mv1y, bd, ww, wo);
-    else mc_block<4>(S, ref, ref1, pw, ph, bx, by, bs, dir, mvx, mvy, mv1x, mv1y, bd, ww, wo);
+    if constexpr (WB) {
+      const int16_t* t = a.wpb + slot * 12;
+      const bool on = t[0] != 0 || t[6] != 0;  // (a weighted list weights all three components)
+      const int ww = on ? (t[2 * c] ? t[2 * c] : 64) : 0, wo = t[2 * c] ? t[2 * c + 1] : 0;
+      const int ww1 = on ? (t[6 + 2 * c] ? t[6 + 2 * c] : 64) : 0, wo1 = t[6 + 2 * c] ? t[6 + 2 * c + 1] : 0;
+      if (c == 0) mc_block<8, true>(S, ref, ref1, pw, ph, bx, by, bs, dir, mvx, mvy, mv1x, mv1y, bd, ww, wo, ww1, wo1);
+      else mc_block<4, true>(S, ref, ref1, pw, ph, bx, by, bs, dir, mvx, mvy, mv1x, mv1y, bd, ww, wo, ww1, wo1);
+    } else {
+      const int ww = (a.wp && dir == hevc::DIR_L0 && r0 == 0) ? a.wp[slot * 6 + 2 * c] : 0;
+      const int wo = ww ? a.wp[slot * 6 + 2 * c + 1] : 0;
+      if (c == 0) mc_block<8>(S, ref, ref1, pw, ph, bx, by, bs, dir, mvx, mvy, mv1x, mv1y, bd, ww, wo);
+      else mc_block<4>(S, ref, ref1, pw, ph, bx, by, bs, dir, mvx, mvy, mv1x, mv1y, bd, ww, wo);
+    }
     for (int i = lane; i < bs * bs; i += 64) {
       const int y = i / bs, x = i - y * bs;
       const int r = static_cast<int>(src[static_cast<size_t>(by + y) * pw + bx + x]) - S.pred[i];
@@ -486,9 +373,10 @@ extern "C" void mivc_launch_hevc_inter(int B, int W, int H, const uint16_t* sy, 
                                        int intra_bias, void* stream, const int16_t* mvb, const uint8_t* dirb,
                                        const uint16_t* f1y, const uint16_t* f1u, const uint16_t* f1v,
                                        const int16_t* wp, const uint16_t* const* xref, const int16_t* mv8, int rdoq,
-                                       int rdoq_lam) {
+                                       int rdoq_lam, const int16_t* wpb) {
   HevcInterArgs a;
   a.wp = wp;
+  a.wpb = wpb;
   a.mv8 = mv8;
   for (int r = 0; r < 3; ++r) {  // xref: [3 x (y, u, v)] of RefPicList0[1 ..] (null: list-0[0])
     a.xref_y[r] = xref && xref[3 * r] ? xref[3 * r] : fy;
@@ -529,11 +417,19 @@ extern "C" void mivc_launch_hevc_inter(int B, int W, int H, const uint16_t* sy, 
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(hevc_p_decide, dim3(a.g.nctb(), B), dim3(64), 0, s, a);
   const dim3 grid(a.g.nctb() * 4, B);
-  if (rdoq) {
-    if (tu_split) hipLaunchKernelGGL((hevc_inter_cu<true, true>), grid, dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((hevc_inter_cu<false, true>), grid, dim3(64), 0, s, a);
+  if (wpb) {  // B pictures with explicit weights (the caller checks: B motion, no list-0 table)
+    if (rdoq) {
+      if (tu_split) hipLaunchKernelGGL((hevc_inter_cu<true, true, true>), grid, dim3(64), 0, s, a);
+      else hipLaunchKernelGGL((hevc_inter_cu<false, true, true>), grid, dim3(64), 0, s, a);
+    } else {
+      if (tu_split) hipLaunchKernelGGL((hevc_inter_cu<true, false, true>), grid, dim3(64), 0, s, a);
+      else hipLaunchKernelGGL((hevc_inter_cu<false, false, true>), grid, dim3(64), 0, s, a);
+    }
+  } else if (rdoq) {
+    if (tu_split) hipLaunchKernelGGL((hevc_inter_cu<true, true, false>), grid, dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((hevc_inter_cu<false, true, false>), grid, dim3(64), 0, s, a);
   } else {
-    if (tu_split) hipLaunchKernelGGL((hevc_inter_cu<true, false>), grid, dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((hevc_inter_cu<false, false>), grid, dim3(64), 0, s, a);
+    if (tu_split) hipLaunchKernelGGL((hevc_inter_cu<true, false, false>), grid, dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((hevc_inter_cu<false, false, false>), grid, dim3(64), 0, s, a);
   }
 }

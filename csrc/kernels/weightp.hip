@@ -11,6 +11,12 @@
 //              prediction p best matches s' is the one whose weighted prediction
 //              ((p * w + 2^(d-1)) >> d) + o best matches s.  encode_inter applies the forward
 //              weight to the chosen prediction (luma and chroma), exactly as a decoder does.
+//   wp_ref8    HEVC B pictures with explicit weights (x265 --weightb): two lists carry two
+//              different weights and the bi candidate combines both, so one inverse-weighted
+//              source does not do.  Instead each list's 8-bit reference proxy is weighted
+//              forward, r' = clip8(((r * w + 32) >> 6) + o), and the searches and decision
+//              kernels run unchanged against the weighted proxies: each approximates the current
+//              picture, and their plain average the explicit bi-prediction.
 #include "kcommon.h"
 
 namespace mivc {
@@ -141,6 +147,30 @@ __global__ __launch_bounds__(256) void wp_src(const uint8_t* __restrict__ src, u
   }
 }
 
+// wt: [B, 2] (w, o) of the luma weight per slot over 2^6; (64, 0): identity (plain copy)
+__global__ __launch_bounds__(256) void wp_ref8(const uint8_t* __restrict__ ref, uint8_t* __restrict__ dst,
+                                               const int* __restrict__ wt, size_t words_per_slot) {
+  const int slot = blockIdx.y;
+  const int w = wt[slot * 2], o = wt[slot * 2 + 1];
+  const uint32_t* s = reinterpret_cast<const uint32_t*>(ref) + slot * words_per_slot;
+  uint32_t* t = reinterpret_cast<uint32_t*>(dst) + slot * words_per_slot;
+  const bool ident = w == 64 && o == 0;
+  for (size_t i = blockIdx.x * 256 + threadIdx.x; i < words_per_slot; i += gridDim.x * 256) {
+    const uint32_t x = s[i];
+    if (ident) {
+      t[i] = x;
+      continue;
+    }
+    uint32_t r = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int b = static_cast<int>((x >> (8 * k)) & 255u);
+      r |= static_cast<uint32_t>(clampi(((b * w + 32) >> 6) + o, 0, 255)) << (8 * k);
+    }
+    t[i] = r;
+  }
+}
+
 }  // namespace gpu
 }  // namespace mivc
 
@@ -168,4 +198,15 @@ extern "C" void mivc_launch_wp_src(const uint8_t* src, uint8_t* dst, const int* 
   const size_t nb = (words + 255) / 256;
   const int blocks = static_cast<int>(nb < 256 ? nb : 256);
   hipLaunchKernelGGL(wp_src, dim3(blocks, B), dim3(256), 0, static_cast<hipStream_t>(stream), src, dst, wt, words);
+}
+
+// returns non-zero for a plane size that is not a positive multiple of 4 bytes
+extern "C" int mivc_launch_wp_ref8(const uint8_t* ref, uint8_t* dst, const int* wt, int B, long long plane_bytes,
+                                   void* stream) {
+  if (B < 1 || plane_bytes < 4 || plane_bytes % 4) return 1;
+  const size_t words = static_cast<size_t>(plane_bytes) / 4;
+  const size_t nb = (words + 255) / 256;
+  const int blocks = static_cast<int>(nb < 256 ? nb : 256);
+  hipLaunchKernelGGL(wp_ref8, dim3(blocks, B), dim3(256), 0, static_cast<hipStream_t>(stream), ref, dst, wt, words);
+  return 0;
 }

@@ -233,6 +233,10 @@ HEVC_PARAMS = {
     "no-b-pyramid": ("pyramid", lambda v: not _flag(v)),
     "tmvp": ("tmvp", _flag),
     "no-tmvp": ("tmvp", lambda v: not _flag(v)),
+    "weightp": ("weightp", _flag),
+    "no-weightp": ("weightp", lambda v: not _flag(v)),
+    "weightb": ("weightb", _flag),
+    "no-weightb": ("weightb", lambda v: not _flag(v)),
     "keyint": ("@keyint", _int_in(1, 100000)),
     "aq-mode": ("*", _aq_mode_hevc),
     "aq-strength": ("aq_strength", _float_in(0.0, 3.0)),

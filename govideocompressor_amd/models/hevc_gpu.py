@@ -164,6 +164,16 @@ class HevcParams:
     weightp: bool = True
     wp_min_mean: float = 2.0
     wp_min_scale: float = 0.08
+    # x265 --weightb (off in x265 medium too): explicit weights in B slices (weighted_bipred_flag;
+    # HEVC has no implicit mode).  Each list's reference is measured against the B picture by the
+    # weightp rule and thresholds above; a list under the thresholds stays unweighted, so a slot may
+    # be weighted on one list only.  The searches and the decision kernels of a weighted step run
+    # against forward-weighted 8-bit proxies of both references (weightp.hip wp_ref8 + their
+    # half-sample planes: two extra proxy sets, allocated only with this knob; steps without a
+    # weighted slot launch nothing extra); hevc_inter_cu's weightb instances predict by the
+    # explicit uni / bi formulas (8.5.3.3.4.3).  Independent of weightp.  Measurements:
+    # profiles/hevc_weightb.md -- opt-in, in no preset
+    weightb: bool = False
     # x265 --ref: active list-0 pictures of a P picture (its nearest earlier reference pictures;
     # models/gop.py hevc_gop_plan).  The farther pictures get 16x16 searches seeded by the
     # distance-scaled list-0[0] vectors (radius ref_range), skipped where the list-0[0] cost is
@@ -195,6 +205,9 @@ class HevcParams:
     def eff_weightp(self) -> bool:
         return bool(self.weightp and not self.intra_only)
 
+    def eff_weightb(self) -> bool:
+        return bool(self.weightb and self.eff_bframes() > 0)
+
     def eff_bframes(self) -> int:
         return 0 if (self.intra_only or self.keyint > 0) else max(0, int(self.bframes))
 
@@ -211,7 +224,7 @@ class HevcParams:
                     cu_qp_delta=int(self.adaptive_qp()), tu_inter_depth=int(self.tu_inter_depth), sdh=int(self.sdh),
                     level_idc=int(self.level_idc), bframes=self.eff_bframes(), tmvp=int(self.tmvp and not self.intra_only),
                     pyramid=int(self.pyramid), ctu64=int(self.ctu64), weightp=int(self.eff_weightp()),
-                    refs=self.eff_refs())
+                    weightb=int(self.eff_weightb()), refs=self.eff_refs())
 
     def frame_qps(self) -> tuple[int, int]:
         qp_p = int(round(self.crf)) if self.crf is not None else int(self.qp)
@@ -319,6 +332,12 @@ class GpuHevcEncoder:
         self.ref8s = [torch.zeros((B, H, W), dtype=torch.uint8, device=dev) for _ in range(self.ref_slots)]
         self.me_hps = [torch.empty(B * 3 * (H + 8) * (W + 8) + 64, dtype=torch.uint8, device=dev)
                        for _ in range(self.ref_slots)]
+        if params.eff_weightb():
+            # forward-weighted proxies of a weighted B step's two references and their half-sample planes
+            if not hasattr(self.hip, "wp_ref8"):
+                raise RuntimeError("weightb needs a kernel library with wp_ref8 and the weightb inter instances (rebuild)")
+            self.ref8w = [torch.zeros((B, H, W), dtype=torch.uint8, device=dev) for _ in range(2)]
+            self.me_hpw = [torch.empty_like(self.me_hps[0]) for _ in range(2)]
         self.mv = torch.zeros((B, nmb, 2), dtype=torch.int16, device=dev)
         self.prev_mv = torch.zeros((B, nmb, 2), dtype=torch.int16, device=dev)
         self.mv_tmp = torch.zeros((B, nmb, 2), dtype=torch.int16, device=dev)
@@ -718,10 +737,14 @@ class GpuHevcEncoder:
         reference from the source statistics (kernels/weightp.hip wp_stats: means and variances
         of the two source pictures' planes).  Returns {step: (host rows [B] of [w, o] x 3 or
         None, device int16 [B, 6] with weight 0 = not weighted, device int32 [B, 3] luma
-        (w, o, log2) for the search's inverse-weighted source)}."""
-        if not self.p.eff_weightp():
-            return {}
-        steps = [(t, pic) for t, pic in enumerate(plan) if pic.kind == "P"]
+        (w, o, log2) for the search's inverse-weighted source)}.
+
+        x265 --weightb: per B picture and slot, one such row per list (list 0 measured against
+        ``pic.l0``, list 1 against ``pic.l1``) by the same rule.  A B step gives (list-0 host rows,
+        device int16 [B, 2, 6], two device int32 [B, 2] luma (w, o) tables -- (64, 0) where the list
+        is not weighted -- for the forward-weighted reference proxies, list-1 host rows)."""
+        wp_on, wb_on = self.p.eff_weightp(), self.p.eff_weightb()
+        steps = [(t, pic) for t, pic in enumerate(plan) if (pic.kind == "P" and wp_on) or (pic.kind == "B" and wb_on)]
         if not steps:
             return {}
         B, F, h, w = y.shape
@@ -737,13 +760,13 @@ class GpuHevcEncoder:
         mean = sh[..., 0::2] / n / unit
         var = np.maximum(sh[..., 1::2] / n / unit ** 2 - mean ** 2, 0.0)
         out = {}
-        for t, pic in steps:
-            m1, m0 = mean[:, pic.d], mean[:, pic.l0]
-            v1, v0 = var[:, pic.d], var[:, pic.l0]
+
+        def measure(cur: int, ref: int):
+            """(rows [B] of [w, o] x 3 or None, device table [B, 6]) of picture ``ref`` predicting ``cur``"""
+            m1, m0 = mean[:, cur], mean[:, ref]
+            v1, v0 = var[:, cur], var[:, ref]
             scale = np.where(v0 > 1e-3, np.sqrt(v1 / np.maximum(v0, 1e-3)), 1.0)
             use = (np.abs(m1[:, 0] - m0[:, 0]) >= self.p.wp_min_mean) | (np.abs(scale[:, 0] - 1) >= self.p.wp_min_scale)
-            if not use.any():
-                continue
             # weight >= 1: the kernels read weight 0 as "this slot is not weighted" (hevc_inter.hip),
             # so a fade to a flat plane (variance -> 0) must not quantise to 0 while the writer
             # still codes the flag -- the decoder would predict offset-only samples
@@ -751,14 +774,43 @@ class GpuHevcEncoder:
             oq = np.clip(np.round(m1 - wq / 64.0 * m0), -128, 127).astype(np.int64)
             rows = [[int(x) for c in range(3) for x in (wq[b, c], oq[b, c])] if use[b] else None for b in range(B)]
             dev = np.zeros((B, 6), np.int16)
+            for b in range(B):
+                if use[b]:
+                    dev[b] = rows[b]
+            return rows, dev
+
+        nwb = 0
+        self.last_weightb = {}  # display index of a weighted B picture -> per slot (list 0 weighted, list 1 weighted)
+        for t, pic in steps:
+            if pic.kind == "B":
+                (rows0, dev0), (rows1, dev1) = measure(pic.d, pic.l0), measure(pic.d, pic.l1)
+                on = [r0 is not None or r1 is not None for r0, r1 in zip(rows0, rows1)]
+                if not any(on):
+                    continue
+                nwb += sum(on)
+                self.last_weightb[pic.d] = [(r0 is not None, r1 is not None) for r0, r1 in zip(rows0, rows1)]
+                wt = []
+                for dv in (dev0, dev1):
+                    x = np.zeros((B, 2), np.int32)
+                    x[:, 0] = np.where(dv[:, 0] != 0, dv[:, 0], 64)
+                    x[:, 1] = np.where(dv[:, 0] != 0, dv[:, 1], 0)
+                    wt.append(torch.from_numpy(x).to(self.dev))
+                out[t] = (rows0, torch.from_numpy(np.stack([dev0, dev1], axis=1)).to(self.dev), wt, rows1)
+                continue
+            rows, dev = measure(pic.d, pic.l0)
+            use = [r is not None for r in rows]
+            if not any(use):
+                continue
             wsrc = np.zeros((B, 3), np.int32)
             wsrc[:, 0], wsrc[:, 2] = 64, 6
             for b in range(B):
                 if use[b]:
-                    dev[b] = rows[b]
                     wsrc[b, 0], wsrc[b, 1] = rows[b][0], rows[b][1]
             out[t] = (rows, torch.from_numpy(dev).to(self.dev), torch.from_numpy(wsrc).to(self.dev))
-        self.stats["weightp_pictures"] = int(sum(sum(r is not None for r in v[0]) for v in out.values()))
+        if wp_on:
+            self.stats["weightp_pictures"] = int(sum(sum(r is not None for r in v[0]) for v in out.values() if len(v) == 3))
+        if wb_on:
+            self.stats["weightb_pictures"] = int(nwb)  # (B step, slot) pairs with a weighted list
         return out
 
     def _plan(self, F: int, cuts_h: np.ndarray, anchors_at) -> list:
@@ -952,7 +1004,7 @@ class GpuHevcEncoder:
                 ref8, hp = self.ref8s[r0], self.me_hps[r0]
                 inter_kw = {}
                 s8 = p(self.src8)
-                if t in wps:
+                if t in wps and pic.kind == "P":
                     # weighted P picture: the searches see the inverse-weighted source proxy
                     # against the unweighted reference (kernels/weightp.hip wp_src)
                     self.hip.wp_src(p(self.src8), p(self.src8w), p(wps[t][2]), B, self.H * self.W, s)
@@ -1027,6 +1079,14 @@ class GpuHevcEncoder:
                                 self.mv.copy_(self.mv_tmp)
                 else:
                     ref8b, hpb = self.ref8s[r1], self.me_hps[r1]
+                    if t in wps:
+                        # weighted B picture: searches and decisions see each list's forward-weighted
+                        # reference proxy (kernels/weightp.hip wp_ref8) and its half-sample planes
+                        with st("halfpel"):
+                            for l, rs in enumerate((r0, r1)):
+                                self.hip.wp_ref8(p(self.ref8s[rs]), p(self.ref8w[l]), p(wps[t][2][l]), B, self.H * self.W, s)
+                                self.hip.me_halfpel(B, self.W, self.H, p(self.ref8w[l]), p(self.me_hpw[l]), s)
+                        ref8, hp, ref8b, hpb = self.ref8w[0], self.me_hpw[0], self.ref8w[1], self.me_hpw[1]
                     with st("me_b"):
                         self._temporal_candidates(pic, ref_lists[pic.l1])
                         self.hip.me(B, self.wmb, self.hmb, p(self.src8), p(ref8), p(self.pm0), p(self.mv),
@@ -1053,6 +1113,8 @@ class GpuHevcEncoder:
                     r1p = self.rec[r1]
                     inter_kw = dict(mvb=p(self.mvb[fin]), dirb=p(self.dirb[fin]), f1y=p(r1p[0]), f1u=p(r1p[1]),
                                     f1v=p(r1p[2]))
+                    if t in wps:
+                        inter_kw["wpb"] = p(wps[t][1])
                 if cuts_c[:, t].any():  # scene cut: every CU of these slots goes intra
                     self.me_cost.masked_fill_(cuts_d[t][:, None], 1 << 26)
                 with st("intra_analyze"):  # open-loop intra candidates where intra may still win
@@ -1118,9 +1180,10 @@ class GpuHevcEncoder:
             nzmap, nzoff = self.nzmaps[kb], self.nzoffs[kb]
             qcol = qps_c[:, t].copy()
             wrow = wps[t][0] if t in wps else None
+            wrow1 = wps[t][3] if t in wps and pic.kind == "B" else None  # list-1 rows (weightb)
             if gpu_entropy:
                 job = self._gpu_entropy_step(t, pic, idr_d, kb, hb, cfg, qps_d[t], qcol, wrow, tmvp, anchor_meta,
-                                             ref_lists, cabac_s)
+                                             ref_lists, cabac_s, wrow1)
                 t1 = time.perf_counter()
                 t_gpu += t1 - t0
             else:
@@ -1142,7 +1205,8 @@ class GpuHevcEncoder:
                 t1 = time.perf_counter()
                 t_gpu += t1 - t0
 
-                def job(done=done, pic=pic, qcol=qcol, ctu=ctu, cu=cu, nz=nz, off=off, lv=lv, i0=idr_d, wrow=wrow):
+                def job(done=done, pic=pic, qcol=qcol, ctu=ctu, cu=cu, nz=nz, off=off, lv=lv, i0=idr_d, wrow=wrow,
+                        wrow1=wrow1):
                     done.synchronize()
                     tj = time.perf_counter()
                     # POC counts display pictures from the latest IDR
@@ -1166,6 +1230,8 @@ class GpuHevcEncoder:
                         fp = dict(base, qp=int(qcol[b]))
                         if wrow is not None and wrow[b] is not None:
                             fp["wp"] = wrow[b]
+                        if wrow1 is not None and wrow1[b] is not None:
+                            fp["wp1"] = wrow1[b]
                         if col is not None:
                             fp["col_cu"] = None if col[0] is None else col[0][b]
                         fps.append(fp)
@@ -1217,7 +1283,8 @@ class GpuHevcEncoder:
                 base["col_refs0"] = [r - i0 for r in col_meta[2]]
         return base
 
-    def _gpu_entropy_step(self, t, pic, i0, kb, hb, cfg, qp_row, qcol, wrow, tmvp, anchor_meta, ref_lists, cabac_s):
+    def _gpu_entropy_step(self, t, pic, i0, kb, hb, cfg, qp_row, qcol, wrow, tmvp, anchor_meta, ref_lists, cabac_s,
+                          wrow1=None):
         """Issue coding step t's GPU entropy on the copy stream (after the step's records are
         final): the nz maps, the CABAC substreams of the B pictures (kernels/hevc_entropy.hip)
         packed into pinned host set ``hb``, and -- for a reference picture with TMVP -- a device
@@ -1265,7 +1332,7 @@ class GpuHevcEncoder:
             anchor_meta[pic.d] = (pic.slot, pic.l0, pic.l1, pic.refs0)
         n = B * self.ent_nsub
 
-        def job(done=done, base=base, qcol=qcol, wrow=wrow, eh=eh, hb=hb):
+        def job(done=done, base=base, qcol=qcol, wrow=wrow, wrow1=wrow1, eh=eh, hb=hb):
             done.synchronize()
             tj = time.perf_counter()
             offs = eh["offs"].numpy().view(np.uint64)
@@ -1285,6 +1352,8 @@ class GpuHevcEncoder:
                 fp = dict(base, qp=int(qcol[b]))
                 if wrow is not None and wrow[b] is not None:
                     fp["wp"] = wrow[b]
+                if wrow1 is not None and wrow1[b] is not None:
+                    fp["wp1"] = wrow1[b]
                 fps.append(fp)
             r = self.host.hevc_assemble_slices(cfg, fps, data, offs, sizes, eh["errs"].numpy(), self.entropy_threads)
             cabac_s[0] += time.perf_counter() - tj

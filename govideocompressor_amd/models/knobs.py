@@ -77,6 +77,7 @@ HEVC = {
     "MIVC_HEVC_RDOQ": "rdoq_level",
     "MIVC_HEVC_RDOQ_LAMBDA": "rdoq_lambda",
     "MIVC_HEVC_AQ_MODE": "aq_mode",
+    "MIVC_HEVC_WEIGHTB": "weightb",
 }
 # bench.py shape knobs (they change what is measured, so they also need --allow-knobs)
 # (MIVC_HIP_LIB: an alternative kernel library, tools/build_variant.py -- same-box A/B timing)

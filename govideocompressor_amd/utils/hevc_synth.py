@@ -178,13 +178,17 @@ def random_stream(host, width: int, height: int, frames: int, seed: int = 0, qp:
 
 def random_gop_stream(host, width: int, height: int, frames: int, bframes: int = 3, seed: int = 0, qp: int = 30,
                       bit_depth: int = 8, tmvp: bool = True, pyramid: bool = False, host_cfg: dict | None = None,
-                      refs: int = 1, **kw) -> tuple[bytes, list]:
+                      refs: int = 1, weights: dict | None = None, b_residual: bool = True, **kw) -> tuple[bytes, list]:
     """Annex-B HEVC stream of one closed GOP with B pictures (models/gop.py hevc_gop_plan:
     I, P anchors, B pictures referencing the pictures on both sides; ``pyramid``: the middle
     B of a run is a reference picture) from random records, with each picture's RPS; TMVP
     takes the collocated picture's records.  Returns the stream and the records per
     *display* index (the decoder outputs pictures in POC order).  ``refs`` > 1: P pictures
-    predict from up to that many earlier reference pictures (x265 --ref; refIdx per CU)."""
+    predict from up to that many earlier reference pictures (x265 --ref; refIdx per CU).
+    ``weights``: display index -> dict of the picture's explicit weights (``wp`` for list 0, ``wp1``
+    for list 1 of a B picture, each [w, o] x (Y, Cb, Cr); needs ``weightp`` / ``weightb`` in
+    ``host_cfg``); ``b_residual`` False: B pictures carry no levels (their decoded samples are
+    the prediction)."""
     from ..models.gop import hevc_gop_plan, hevc_ref_slots
 
     rng = np.random.default_rng(seed)
@@ -198,8 +202,11 @@ def random_gop_stream(host, width: int, height: int, frames: int, bframes: int =
         fqp = int(np.clip(qp + rng.integers(-3, 4), 0, 51))
         r = random_records(rng, width, height, pslice=pic.kind != "I", bit_depth=bit_depth, bslice=pic.kind == "B",
                            nref=(max(1, len(pic.refs0)), 1), **kw)
+        if pic.kind == "B" and not b_residual:
+            r = r[:2] + tuple(np.zeros_like(c) for c in r[2:])
         fp = dict(idr=int(pic.kind == "I"), poc=pic.d, qp=fqp, slice_type={"I": 2, "P": 1, "B": 0}[pic.kind],
                   nal_ref=int(pic.ref), rps=[(d, int(u)) for d, u in pic.rps])
+        fp.update((weights or {}).get(pic.d, {}))
         if pic.kind != "I":
             fp["ref_poc0"] = pic.l0
             fp["refs0"] = list(pic.refs0)

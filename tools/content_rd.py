@@ -130,6 +130,10 @@ HEVC_CONFIGS = {
     "ba_b3": dict(b_adapt=1, bframes=3),
     "ba_b3bias100": dict(b_adapt=1, bframes=3, b_bias=100),
     "ba_b4": dict(b_adapt=1, bframes=4),
+    # x265 --weightb: explicit weights in B slices (profiles/hevc_weightb.md)
+    "weightb": dict(weightb=True),
+    "bf3wb": dict(bframes=3, b_qp_offset=2, weightb=True),
+    "ba_b3wb": dict(b_adapt=1, bframes=3, weightb=True),
     # x265 medium's --tu-inter-depth 1 and --signhide, re-measured on the round-6 encoder
     "tud1": dict(tu_inter_depth=1),
     "sdh": dict(sdh=True),
@@ -163,6 +167,8 @@ def run(args):
             y, u, v = clips[kind]
             for crf in crfs:
                 enc.p.crf = float(crf)
+                if getattr(getattr(enc, "stage_timer", None), "enabled", False):
+                    enc.stage_timer.reset()  # stage_ms of this call alone
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 res = enc.encode(y, u, v, metrics=True)
@@ -177,6 +183,10 @@ def run(args):
                           spatial_fix_ratio=stats.get("spatial_fix_ratio"),
                           spatial_conv_ratio=stats.get("spatial_conv_ratio"),
                           direct_unavail_ratio=stats.get("direct_unavail_ratio"))
+                if "weightb_pictures" in stats:
+                    pt["weightb_pictures"] = stats["weightb_pictures"]
+                if getattr(enc, "stage_ms", None):  # MIVC_STAGE_TIMING=1: device time per stage of this call
+                    pt["stage_ms"] = dict(enc.stage_ms)
                 out["points"].append(pt)
                 print(json.dumps(pt), flush=True)
         enc.close()
