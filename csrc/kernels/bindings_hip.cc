@@ -143,11 +143,14 @@ void mivc_launch_hevc_inter(int B, int W, int H, const uint16_t* sy, const uint1
                             int tu_split, int sdh, int intra_bias, void* stream, const int16_t* mvb,
                             const uint8_t* dirb, const uint16_t* f1y, const uint16_t* f1u, const uint16_t* f1v,
                             const int16_t* wp, const uint16_t* const* xref, const int16_t* mv8, int rdoq, int rdoq_lam,
-                            const int16_t* wpb);
+                            const int16_t* wpb, const int* rd_lamq);
 int mivc_launch_hevc_mc_probe(int ncase, const uint16_t* ref0, const uint16_t* ref1, int pw, int ph, const int16_t* cases,
                               uint16_t* out, int nt, int n, int dir, int bd, int ww, int wo, int ww1, int wo1, int wb,
                               int lean, void* stream);
 int mivc_launch_wp_ref8(const uint8_t* ref, uint8_t* dst, const int* wt, int B, long long plane_bytes, void* stream);
+int mivc_launch_hevc_rd_cbf_probe(int nblk, const uint16_t* src, const uint16_t* pred, int16_t* lev, uint16_t* rec, int* flag,
+                                  long long* terms, int log2n, int bd, int qp, int sdh, int rdoq, int rdoq_lam, int lamq,
+                                  void* stream);
 int mivc_launch_hevc_tq_probe(int nblk, const int* res, int16_t* lev, int* rec, int* flag, int log2n, int bd, int qp,
                               int intra, int dst, int scan, int sdh, int rdoq, int rdoq_lam, int mfma, void* stream);
 void mivc_launch_hevc_b(int mode, int B, int wmb, int hmb, const uint8_t* src_y, const uint8_t* ref0, const uint8_t* ref1,
@@ -624,7 +627,10 @@ PYBIND11_MODULE(_hip, m) {
                          uintptr_t cu_, uintptr_t cv, uintptr_t qp, uintptr_t run, uintptr_t cand, uintptr_t mv,
                          uintptr_t me_cost, int bd, uintptr_t stream, int tu_split, int sdh, int intra_bias,
                          uintptr_t mvb, uintptr_t dirb, uintptr_t f1y, uintptr_t f1u, uintptr_t f1v, uintptr_t wp,
-                         std::vector<uintptr_t> xref, uintptr_t mv8, int rdoq, int rdoq_lam, uintptr_t wpb) {
+                         std::vector<uintptr_t> xref, uintptr_t mv8, int rdoq, int rdoq_lam, uintptr_t wpb, int rd_cbf,
+                         uintptr_t rd_lamq) {
+    // rd_cbf: every TU's levels checked against none (hevc_rdcbf.h); rd_lamq: int32 [52], lambda per QpY
+    if ((rd_cbf != 0) != (rd_lamq != 0)) throw std::invalid_argument("hevc_inter: rd_cbf and its rd_lamq table come together");
     // wpb: x265 --weightb, int16 [B][2][6] list-0 / list-1 weights of a B picture
     if (wpb && (!dirb || wp || !xref.empty())) throw std::invalid_argument("hevc_inter: wpb belongs to B pictures (dirb, no wp / xref)");
     if (rdoq < 0 || rdoq > 2 || rdoq_lam < 0 || rdoq_lam > 1472) throw std::invalid_argument("hevc_inter: rdoq in 0..2, rdoq_lam in 0..1472");
@@ -638,14 +644,14 @@ PYBIND11_MODULE(_hip, m) {
                            P<int16_t>(cy), P<int16_t>(cu_), P<int16_t>(cv), P<int>(qp), P<int8_t>(run), P<int>(cand),
                            P<int16_t>(mv), P<int>(me_cost), bd, tu_split, sdh, intra_bias, S(stream), P<int16_t>(mvb),
                            P<uint8_t>(dirb), P<uint16_t>(f1y), P<uint16_t>(f1u), P<uint16_t>(f1v), P<int16_t>(wp), xr,
-                           P<int16_t>(mv8), rdoq, rdoq_lam, P<int16_t>(wpb));
+                           P<int16_t>(mv8), rdoq, rdoq_lam, P<int16_t>(wpb), P<int>(rd_lamq));
   }, py::arg("B"), py::arg("W"), py::arg("H"), py::arg("sy"), py::arg("su"), py::arg("sv"), py::arg("fy"), py::arg("fu"),
      py::arg("fv"), py::arg("ry"), py::arg("ru"), py::arg("rv"), py::arg("ctu"), py::arg("cu"), py::arg("cy"),
      py::arg("cu_"), py::arg("cv"), py::arg("qp"), py::arg("run"), py::arg("cand"), py::arg("mv"), py::arg("me_cost"),
      py::arg("bd"), py::arg("stream"), py::arg("tu_split") = 0, py::arg("sdh") = 0, py::arg("intra_bias") = 0,
      py::arg("mvb") = 0, py::arg("dirb") = 0, py::arg("f1y") = 0, py::arg("f1u") = 0, py::arg("f1v") = 0,
      py::arg("wp") = 0, py::arg("xref") = std::vector<uintptr_t>{}, py::arg("mv8") = 0, py::arg("rdoq") = 0,
-     py::arg("rdoq_lam") = 0, py::arg("wpb") = 0);
+     py::arg("rdoq_lam") = 0, py::arg("wpb") = 0, py::arg("rd_cbf") = 0, py::arg("rd_lamq") = 0);
   // mc_block (hevc_mc.h) on ncase blocks of planted reference planes [ph, pw] (uint16): cases
   // int16 [ncase, 6] = block x, y, list-0 vector, list-1 vector; out uint16 [ncase, n * n]
   m.def("hevc_mc_probe", [](int ncase, uintptr_t ref0, uintptr_t ref1, int pw, int ph, uintptr_t cases, uintptr_t out, int nt,
@@ -673,6 +679,19 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("nblk"), py::arg("res"), py::arg("lev"), py::arg("rec"), py::arg("flag"), py::arg("log2n"), py::arg("bd"),
      py::arg("qp"), py::arg("intra"), py::arg("dst"), py::arg("scan"), py::arg("sdh"), py::arg("rdoq"),
      py::arg("rdoq_lam"), py::arg("mfma"), py::arg("stream"));
+  // hv::rd_cbf_tu after hv::transform_quant_block (inter, diagonal scan) on nblk source / prediction
+  // blocks [nblk, n, n] (uint16): levels (int16), reconstructed samples (uint16), the flag (int32) and
+  // D0, D1, Rb (int64 [nblk, 3]) per block
+  m.def("hevc_rd_cbf_probe", [](int nblk, uintptr_t src, uintptr_t pred, uintptr_t lev, uintptr_t rec, uintptr_t flag,
+                                uintptr_t terms, int log2n, int bd, int qp, int sdh, int rdoq, int rdoq_lam, int lamq,
+                                uintptr_t stream) {
+    if (mivc_launch_hevc_rd_cbf_probe(nblk, P<uint16_t>(src), P<uint16_t>(pred), P<int16_t>(lev), P<uint16_t>(rec), P<int>(flag),
+                                      P<long long>(terms), log2n, bd, qp, sdh, rdoq, rdoq_lam, lamq, S(stream)) != 0)
+      throw std::invalid_argument("hevc_rd_cbf_probe: log2n 2..5, bd 8 / 10, qp 0..51 + 6 (bd - 8), rdoq 0..2, "
+                                  "rdoq_lam 0..1472, lamq 0..2^23");
+  }, py::arg("nblk"), py::arg("src"), py::arg("pred"), py::arg("lev"), py::arg("rec"), py::arg("flag"), py::arg("terms"),
+     py::arg("log2n"), py::arg("bd"), py::arg("qp"), py::arg("sdh"), py::arg("rdoq"), py::arg("rdoq_lam"), py::arg("lamq"),
+     py::arg("stream"));
   m.def("hevc_b", [](int mode, int B, int wmb, int hmb, uintptr_t src, uintptr_t ref0, uintptr_t ref1, uintptr_t hp0,
                      uintptr_t hp1, uintptr_t mv0, uintptr_t mv1, uintptr_t cost0, uintptr_t cost1, uintptr_t pm0,
                      uintptr_t pm1, uintptr_t tmv, uintptr_t tdir, uintptr_t mvb_in, uintptr_t dir_in, uintptr_t mvb_out,

@@ -26,6 +26,7 @@ Main (8-bit) and Main 10 share one code path: samples are uint16 on the device.
 from __future__ import annotations
 
 import concurrent.futures as cf
+import math
 import os
 import time
 from dataclasses import dataclass, field
@@ -103,6 +104,17 @@ class HevcParams:
     # 7 % -- opt-in, in no preset
     rdoq_level: int = 0
     rdoq_lambda: float = 0.5
+    # Rate-distortion check of inter residuals against none (csrc/kernels/hevc_rdcbf.h; the null-cost
+    # half of x265 --rd 3, which has no switch of its own): after a TU of an inter CU is quantised
+    # (sign data hiding and RDOQ included) it keeps its levels only when
+    # 256 * D1 + lamq * (Rb + 18) < 256 * D0 + lamq * 8, with D0 / D1 the SSD of prediction /
+    # reconstruction, Rb the levels' rate from RDOQ's static bin costs (1 / 16 bit) and lamq HM's SSD
+    # lambda 0.57 * 2^((QpY - 12) / 3) * 4^(bit_depth - 8) * 16 times ``rd_cbf_lambda``, tabulated
+    # per QpY on the host.  Luma and chroma, with the residual quadtree every candidate TU; a
+    # cleared CU can become a skip CU in the writer.  No syntax of its own; intra CUs are not
+    # touched.  Not measured yet (profiles/hevc_rd_cbf.md) -- opt-in, in no preset
+    rd_cbf: bool = False
+    rd_cbf_lambda: float = 1.0
     # lambda multiples added to the open-loop intra cost of a 16x16 quadrant in P pictures
     # before the inter / intra decision (the closed loop makes intra dearer than its
     # open-loop SATD says)
@@ -232,6 +244,13 @@ class HevcParams:
         return max(0, qp_p - self.ip_offset), qp_p
 
 
+def rd_cbf_lamq_table(rd_cbf_lambda: float, bit_depth: int) -> list[int]:
+    """``HevcParams.rd_cbf``: the SSD lambda of every QpY 0..51 in 1 / 16 units, the integers
+    hevc_inter_cu's check reads (float64 here, none in the kernel)."""
+    return [int(math.floor(float(rd_cbf_lambda) * 0.57 * 2.0 ** ((q - 12) / 3.0) * 4.0 ** (bit_depth - 8) * 16.0 + 0.5))
+            for q in range(52)]
+
+
 @dataclass
 class HevcSegmentResult:
     bitstream: bytes
@@ -291,6 +310,8 @@ class GpuHevcEncoder:
             raise ValueError("rdoq_level must be 0 (off), 1 (levels) or 2 (levels and 4x4 groups)")
         if not 0.0 < float(params.rdoq_lambda) <= 4.0:
             raise ValueError("rdoq_lambda must be in (0, 4]")
+        if not 0.0 < float(params.rd_cbf_lambda) <= 4.0:
+            raise ValueError("rd_cbf_lambda must be in (0, 4]")
         self.p = params
         self.B = int(slots)
         d = torch.device(device)
@@ -311,6 +332,11 @@ class GpuHevcEncoder:
                     torch.zeros((B, H // 2, W // 2), dtype=dt, device=dev))
 
         self.src = planes()
+        # rd_cbf: the lambda table of the inter reconstruction launches (P and B pictures)
+        self.rd_cbf_kw = {}
+        if params.rd_cbf and not params.intra_only:
+            self.rd_lamq = torch.tensor(rd_cbf_lamq_table(params.rd_cbf_lambda, params.bit_depth), dtype=torch.int32, device=dev)
+            self.rd_cbf_kw = dict(rd_cbf=1, rd_lamq=self.rd_lamq.data_ptr())
         self.nb = params.eff_bframes()
         self.nrefs = params.eff_refs()
         # reconstruction buffers: one per DPB slot of a reference picture (models/gop.py
@@ -1127,7 +1153,7 @@ class GpuHevcEncoder:
                                         p(ref[1]), p(ref[2]), p(cur[0]), p(cur[1]), p(cur[2]), p(self.ctu), p(self.cu),
                                         p(self.coef[0]), p(self.coef[1]), p(self.coef[2]), p(self.ctb_qp), p(self.run),
                                         p(self.cand), p(self.mv), p(self.me_cost), bd, s, int(self.p.tu_inter_depth),
-                                        int(self.p.sdh), int(self.p.intra_bias_p), **inter_kw, **rdoq)
+                                        int(self.p.sdh), int(self.p.intra_bias_p), **inter_kw, **rdoq, **self.rd_cbf_kw)
                 with st("intra_recon"):
                     self.hip.hevc_intra(*intra_args, 0, 1, p(self.err), s, int(self.p.sdh), 0,
                                         int(self.p.ctu64), **rdoq)   # intra CUs, wavefront

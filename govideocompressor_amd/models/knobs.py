@@ -76,6 +76,8 @@ HEVC = {
     "MIVC_HEVC_SDH": "sdh",
     "MIVC_HEVC_RDOQ": "rdoq_level",
     "MIVC_HEVC_RDOQ_LAMBDA": "rdoq_lambda",
+    "MIVC_HEVC_RD_CBF": "rd_cbf",
+    "MIVC_HEVC_RD_CBF_LAMBDA": "rd_cbf_lambda",
     "MIVC_HEVC_AQ_MODE": "aq_mode",
     "MIVC_HEVC_WEIGHTB": "weightb",
 }

@@ -107,6 +107,14 @@ HEVC_CONFIGS = {
     "rdoq2l050": dict(rdoq_level=2, rdoq_lambda=0.5),
     "rdoq2l075": dict(rdoq_level=2, rdoq_lambda=0.75),
     "rdoq2l150": dict(rdoq_level=2, rdoq_lambda=1.5),
+    # HevcParams.rd_cbf: inter TUs keep their levels only when they pay for themselves (SSD +
+    # lambda * bits against no levels) and its lambda multiplier (profiles/hevc_rd_cbf.md)
+    "rdcbf": dict(rd_cbf=True),
+    "rdcbf_l050": dict(rd_cbf=True, rd_cbf_lambda=0.5),
+    "rdcbf_l150": dict(rd_cbf=True, rd_cbf_lambda=1.5),
+    "rdcbf_l200": dict(rd_cbf=True, rd_cbf_lambda=2.0),
+    "rdcbf_rdoq1": dict(rd_cbf=True, rdoq_level=1, rdoq_lambda=0.5),
+    "rdcbf_tu": dict(rd_cbf=True, tu_inter_depth=1),
     "bf0": dict(bframes=0),
     "bf3": dict(bframes=3, b_qp_offset=2),
     "bqp2": dict(b_qp_offset=2),
