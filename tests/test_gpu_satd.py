@@ -44,7 +44,6 @@ def test_satd_primitives_match_numpy(mode):
 
 # ---------------------------------------------------------------- trellis forms (h264_trellis.h)
 CF = np.array([[1, 1, 1, 1], [2, 1, -1, -2], [1, -1, -1, 1], [1, -2, 2, -1]], np.int64)
-ZZ = [0, 1, 4, 8, 5, 2, 3, 6, 9, 12, 13, 10, 7, 11, 14, 15]
 MF = [[13107, 5243, 8066], [11916, 4660, 7490], [10082, 4194, 6554], [9362, 3647, 5825], [8192, 3355, 5243],
       [7282, 2893, 4559]]
 
@@ -55,37 +54,9 @@ def _cls(r):
 
 
 def _trellis_ref(w, qp, start):
-    """float64 model of the serial greedy pass (trellis_lite4x4)."""
-    qbits, mf = 15 + qp // 6, MF[qp % 6]
-    lam = 0.85 * 2.0 ** ((qp - 12) / 3)
-    inv = [1 / 16, 1 / 100, 1 / 40]
-
-    def bits(level, seen):
-        b = 1.35 + (0.25 if seen else 2.2) + 1.0
-        if level == 1:
-            return b + 0.6
-        b += 1.7 + 0.9 * min(level - 2, 13)
-        if level > 15:
-            b += 2.0 * (int(level - 14).bit_length() - 1) + 1.0
-        return b
-
-    out = np.zeros(16, np.int64)
-    seen = False
-    for i in range(15, start - 1, -1):
-        r = ZZ[i]
-        a, m = abs(int(w[r])), mf[_cls(r)]
-        zr = (a * m + (1 << (qbits - 1))) >> qbits
-        step = (1 << qbits) / m
-        best, bl = a * a * inv[_cls(r)] + lam * (0.55 if seen else 0.0), 0
-        for level in (zr - 1, zr):
-            if level < 1:
-                continue
-            j = (a - level * step) ** 2 * inv[_cls(r)] + lam * bits(level, seen)
-            if j < best:
-                best, bl = j, level
-        out[r] = -bl if w[r] < 0 else bl
-        seen |= bl != 0
-    return out
+    """float64 model of the serial greedy pass (trellis_lite4x4): tests/ref_models_h264_inter.py"""
+    from ref_models_h264_inter import trellis4
+    return trellis4(w, qp, start)
 
 
 @pytest.mark.parametrize("qp", [12, 24, 33, 45])
