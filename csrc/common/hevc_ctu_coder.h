@@ -299,6 +299,8 @@ struct CoderPic {
   int ref_poc[2], num_ref[2], list_poc[2][4];
   // collocated picture (8.5.3.2.8): records (null: intra / none), POC and its lists' POCs
   int col_set, col_poc, col_ref_poc[2], col_list_poc[2][4];
+  // independent slices of whole CTU rows (hevc_tables.h slice_of_row); 1: the picture is one slice
+  int slices;
 };
 
 // level source: packed non-zero 4x4 blocks (levels != null), else coefficient planes;
@@ -486,6 +488,11 @@ struct CtuCoder {
   // quantization group coded its delta, and its qPY_PRED
   int qp_prev = 0, qp_ctb = 0, qp_pred_cur = 0;
   bool qp_coded = false;
+  // luma rows [slice_y0, slice_y1) of the slice of the CTU being coded (code_ctu; the whole
+  // picture with one slice): samples outside belong to another slice and are not available
+  // (6.4.1).  The lower bound matters with WPP: the next slice's first row waits for nothing
+  // and may already be coded
+  int slice_y0 = 0, slice_y1 = 0;
   // non-zero 4x4 sub-blocks of the current 32x32 block
   uint64_t nz_luma = 0;
   uint32_t nz_chroma[2] = {0, 0};
@@ -525,6 +532,8 @@ struct CtuCoder {
     st = CoderStats();
     qp_ctb = qp_pred_cur = 0;
     qp_coded = false;
+    slice_y0 = 0;
+    slice_y1 = P->H;
     nz_luma = 0;
     nz_chroma[0] = nz_chroma[1] = 0;
     ctb_base = 0;
@@ -552,10 +561,13 @@ struct CtuCoder {
   HV_FN size_t g(int x, int y) const __restrict__ { return static_cast<size_t>(y >> 3) * w8 + (x >> 3); }
   HV_FN size_t g4(int x, int y) const __restrict__ { return static_cast<size_t>(y >> 2) * (2 * w8) + (x >> 2); }
   HV_FN bool inside(int x, int y) const __restrict__ { return x >= 0 && y >= 0 && x < W && y < H; }
+  // inside the picture and the current CTU's slice (runs of whole CTU rows: the slice's rows
+  // stand in for the picture's in the test, at the cost of inside())
+  HV_FN bool in_slice(int x, int y) const __restrict__ { return x >= 0 && x < W && y >= slice_y0 && y < slice_y1; }
   // 6.4.1 z-scan availability at 8x8 granularity (the granule is coded iff already visited)
   HV_FN bool avail(int x, int y) const __restrict__ {
     HV_GLOBAL(S.coded);
-    return inside(x, y) && S.coded[g(x, y)];
+    return in_slice(x, y) && S.coded[g(x, y)];
   }
 
   // records of the current CTU staged in faster memory (GPU): [4 blocks in z-order][16 granules]
@@ -601,11 +613,12 @@ struct CtuCoder {
       return;
     }
     if (rx > 0) e.encode(0, ctx[CTX_SAO_MERGE]);
-    if (ry > 0 && same_sao(t, ctu_sao(rx, ry - 1))) {
+    const bool up = (ry << L) > slice_y0;  // the CTU above is in this slice
+    if (up && same_sao(t, ctu_sao(rx, ry - 1))) {
       e.encode(1, ctx[CTX_SAO_MERGE]);
       return;
     }
-    if (ry > 0) e.encode(0, ctx[CTX_SAO_MERGE]);
+    if (up) e.encode(0, ctx[CTX_SAO_MERGE]);
     const int cmax = (1 << (hv_min(P->bit_depth, 10) - 5)) - 1;
     for (int ci = 0; ci < 3; ++ci) {
       const int type = t.sao_type[ci ? 1 : 0];
@@ -967,16 +980,16 @@ struct CtuCoder {
     const size_t k = g(hv_clamp(xn, 0, W - 1), hv_clamp(yn, 0, H - 1));
     const uint8_t cd = S.coded[k];
     const int8_t sk = S.skip[k];
-    return (inside(xn, yn) && cd && sk) ? 1 : 0;
+    return (in_slice(xn, yn) && cd && sk) ? 1 : 0;
   }
   HV_FN int nb_deeper(int xn, int yn, int d) const __restrict__ {
     const size_t k = g(hv_clamp(xn, 0, W - 1), hv_clamp(yn, 0, H - 1));
     const uint8_t cd = S.coded[k];
     const int8_t dp = S.depth[k];
-    return (inside(xn, yn) && cd && dp > d) ? 1 : 0;
+    return (in_slice(xn, yn) && cd && dp > d) ? 1 : 0;
   }
   HV_FN Nb probe(int xn, int yn) const __restrict__ {
-    const bool in = inside(xn, yn);
+    const bool in = in_slice(xn, yn);
     const size_t k = g(hv_clamp(xn, 0, W - 1), hv_clamp(yn, 0, H - 1));
     const uint8_t cd = S.coded[k];
     const int8_t pr = S.pred[k];
@@ -1364,7 +1377,7 @@ struct CtuCoder {
     const uint8_t cd = S.coded[g(xc, yc)];
     const int8_t pr = S.pred[g(xc, yc)];
     const int md = S.mode4[g4(xc, yc)];
-    if (!inside(xn, yn) || !cd || pr != CU_INTRA) return 1;
+    if (!in_slice(xn, yn) || !cd || pr != CU_INTRA) return 1;
     if (above && (yn >> L) != (yk >> L)) return 1;
     return md;
   }
@@ -1613,16 +1626,24 @@ struct CtuCoder {
     if (P->cu_qp_delta) qp_prev = q;
   }
 
-  // SAO + coding quadtree of CTU (rx, ry) and its end_of_slice_segment_flag; with WPP, a
-  // row's last CTU also codes end_of_subset_one_bit, flushes and byte-aligns its substream
+  // SAO + coding quadtree of CTU (rx, ry) and its end_of_slice_segment_flag (1 at the last CTU
+  // of each slice); with WPP, a row's last CTU that does not end its slice also codes
+  // end_of_subset_one_bit, and every row's last CTU flushes and byte-aligns its substream.
+  // A slice's first CTU needs a coder fresh from begin() (contexts, engine, qPY_PREV).
   HV_BIG void code_ctu(int rx, int ry) __restrict__ {
     HV_LDS(this);
     HV_LDS(ctx);
     HV_LDS(P);
     const ProfScope prof_scope(prof, CP_CTU);
+    const int ns = P->slices, hctu = P->hctu;
+    if (ns > 1) {
+      const int sl = slice_of_row(ry, ns, hctu);
+      slice_y0 = slice_first_row(sl, ns, hctu) << L;
+      slice_y1 = hv_min(slice_first_row(sl + 1, ns, hctu) << L, H);
+    }
     if (P->sao) write_sao(rx, ry);
     write_ctu(rx, ry);
-    const bool last = ry == P->hctu - 1 && rx == P->wctu - 1;
+    const bool last = rx == P->wctu - 1 && (ry == hctu - 1 || (ns > 1 && row_starts_slice(ry + 1, ns, hctu)));
     e.terminate(last);  // end_of_slice_segment_flag
     if (P->wpp && rx == P->wctu - 1 && !last) e.terminate(1);  // end_of_subset_one_bit
     if (last || (P->wpp && rx == P->wctu - 1)) {

@@ -18,6 +18,18 @@ constexpr int kCtb = 1 << kCtbLog2;
 constexpr int kMinCbLog2 = 3;                // 8x8 minimum coding block
 constexpr int kCusPerCtb = (kCtb / 8) * (kCtb / 8);  // 8x8 granules per CTB (z-order)
 
+// ---------------------------------------------------------------- slices (x265 --slices)
+// A picture of hctu CTU rows coded as S independent slices of whole CTU rows, 1 <= S <= hctu:
+// monotone in r, steps by at most one per row, no slice empty.  The one definition the host
+// writer, the shared CTU coder and the kernels use.
+constexpr int kMaxSlices = 16;
+MIVC_HD int slice_of_row(int r, int S, int hctu) { return (r * S) / hctu; }
+MIVC_HD bool row_starts_slice(int r, int S, int hctu) {
+  return r == 0 || slice_of_row(r, S, hctu) != slice_of_row(r - 1, S, hctu);
+}
+// first CTU row of slice s (the smallest r with slice_of_row(r) == s); s == S gives hctu
+MIVC_HD int slice_first_row(int s, int S, int hctu) { return (s * hctu + S - 1) / S; }
+
 // ---------------------------------------------------------------- intra prediction (8.4.4.2.6)
 // intraPredAngle for predModeIntra 0..34 (0/1 planar/DC unused)
 static constexpr int8_t kIntraPredAngle[35] = {0,   0,   32,  26,  21,  17,  13,  9,   5,  2,  0,  -2,

@@ -370,12 +370,15 @@ hevc::HevcConfig hevc_cfg_from(const py::dict& d) {
   c.weightp = dget<int>(d, "weightp", 0);
   c.weightb = dget<int>(d, "weightb", 0);
   c.refs = dget<int>(d, "refs", 1);
+  c.slices = dget<int>(d, "slices", 1);
   if (c.refs < 1 || c.refs > hevc::kMaxRefs) throw std::runtime_error("HEVC: refs in 1..4");
   if (c.tu_inter_depth < 0 || c.tu_inter_depth > 1) throw std::runtime_error("HEVC: tu_inter_depth in 0..1");
   if (c.threads < 1 || c.threads > 256) throw std::runtime_error("HEVC: threads in 1..256");
   if (c.width <= 0 || c.height <= 0 || (c.width & 1) || (c.height & 1)) throw std::runtime_error("HEVC: bad size");
   if (c.bit_depth != 8 && c.bit_depth != 10) throw std::runtime_error("HEVC: bit_depth must be 8 or 10");
   if (c.max_merge < 1 || c.max_merge > 5) throw std::runtime_error("HEVC: max_merge in 1..5");
+  if (c.slices < 1 || c.slices > std::min(hevc::kMaxSlices, c.hctu()))
+    throw std::runtime_error("HEVC: slices in 1..min(16, CTU rows)");
   return c;
 }
 
@@ -926,6 +929,9 @@ PYBIND11_MODULE(_host, m) {
       },
       py::arg("cfg"), py::arg("frame"), py::arg("ctu"), py::arg("cu"), py::arg("coef_y"), py::arg("coef_cb"),
       py::arg("coef_cr"));
+  // slice geometry (hevc_tables.h): the slice of CTU row r, and whether row r starts a slice
+  m.def("hevc_slice_of_row", [](int r, int slices, int hctu) { return hevc::slice_of_row(r, slices, hctu); });
+  m.def("hevc_row_starts_slice", [](int r, int slices, int hctu) { return hevc::row_starts_slice(r, slices, hctu); });
   m.def("hevc_coder_pic", [](const py::dict& cfg, const py::dict& fp) {
     // the GPU entropy kernel's view of a picture (hevc_ctu_coder.h CoderPic) as bytes
     const hevc::HevcConfig c = hevc_cfg_from(cfg);
@@ -944,7 +950,7 @@ PYBIND11_MODULE(_host, m) {
         // substream r of picture b is data[offs[b * nsub + r] ..][: sizes[b * nsub + r]]
         const hevc::HevcConfig c = hevc_cfg_from(cfg);
         const py::ssize_t B = static_cast<py::ssize_t>(frames.size());
-        const int nsub = c.wpp ? c.hctu() : 1;
+        const int nsub = c.wpp ? c.hctu() : c.slices;
         const py::ssize_t n = B * nsub;
         if (offs.size() < n + 1 || sizes.size() < n || errs.size() < n) throw std::runtime_error("substream tables: wrong size");
         const uint64_t* po = offs.data();

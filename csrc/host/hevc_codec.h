@@ -6,8 +6,8 @@
 // 32/16/8, PART_2Nx2N, TU = CU (max_transform_hierarchy_depth 0), 35 intra modes
 // with DM chroma, P slices with one reference picture (merge/skip + AMVP), one QP per
 // CTB through cu_qp_delta (adaptive quantisation; or one QP per slice), deblocking and
-// SAO, WPP substreams (every picture is one slice; pictures entropy-code in parallel on
-// host threads).
+// SAO, WPP substreams (a picture is one slice, or HevcConfig::slices independent slices of
+// whole CTU rows; pictures entropy-code in parallel on host threads).
 //
 // Reference parity: `-vcodec libx265 -crf 26` (server.go:67-68, client.go:115).
 #pragma once
@@ -52,6 +52,9 @@ struct HevcConfig {
   // x265 --ref: the most active list-0 pictures of a P slice (HevcFrameParams::num_ref); sizes
   // the DPB (sps_max_dec_pic_buffering)
   int refs = 1;
+  // x265 --slices: independent slices per picture, each a run of whole CTU rows
+  // (hevc_tables.h slice_of_row), one NAL each; 1 <= slices <= min(16, hctu())
+  int slices = 1;
   int ctb_log2() const { return ctu64 ? 6 : kCtbLog2; }
   int wctu() const { return (coded_width() + (1 << ctb_log2()) - 1) >> ctb_log2(); }
   int hctu() const { return (coded_height() + (1 << ctb_log2()) - 1) >> ctb_log2(); }
@@ -128,7 +131,8 @@ struct PackedLevels {
   size_t nblocks = 0;  // blocks available in `levels` (bounds check)
 };
 
-// One slice NAL (Annex-B) for a whole picture.  ctu: [wctb*hctb]; cu: [wctb*hctb*16]
+// The slice NALs (Annex-B) of a whole picture: one, or HevcConfig::slices in address order;
+// the statistics are sums over them.  ctu: [wctb*hctb]; cu: [wctb*hctb*16]
 // (z-order granules); coef planes sized like the coded picture (luma) / half (chroma), or
 // null with `packed` given.
 std::vector<uint8_t> hevc_write_slice(const HevcConfig& cfg, const HevcFrameParams& fp, const CtuInfo* ctu,
@@ -141,9 +145,9 @@ std::vector<uint8_t> hevc_write_slice(const HevcConfig& cfg, const HevcFramePara
 // reference / collocated POCs (the collocated records pointer is passed separately)
 CoderPic hevc_coder_pic(const HevcConfig& cfg, const HevcFrameParams& fp);
 
-// One slice NAL from substreams coded elsewhere (the GPU entropy kernel): the slice header of
-// `fp`, the entry points of the nsub substreams (one per CTU row with WPP, else one), the
-// substreams, emulation prevention -- byte-identical to hevc_write_slice on the same records.
+// A picture's slice NALs from substreams coded elsewhere (the GPU entropy kernel): per slice
+// the slice header of `fp`, the entry points of its substreams (nsub in all: one per CTU row
+// with WPP, else one per slice), the substreams, emulation prevention -- byte-identical to hevc_write_slice on the same records.
 std::vector<uint8_t> hevc_assemble_slice(const HevcConfig& cfg, const HevcFrameParams& fp, const uint8_t* const* sub,
                                          const uint32_t* sizes, int nsub);
 

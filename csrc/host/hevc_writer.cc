@@ -185,7 +185,8 @@ std::vector<uint8_t> hevc_parameter_sets(const HevcConfig& c) {
     bw.put_bit(0);  // transquant_bypass_enabled_flag
     bw.put_bit(0);  // tiles_enabled_flag
     bw.put_bit(c.wpp ? 1 : 0);  // entropy_coding_sync_enabled_flag
-    bw.put_bit(0);  // pps_loop_filter_across_slices_enabled_flag
+    // several slices: deblocking and SAO run across their edges, as across any CTU edge
+    bw.put_bit(c.slices > 1 ? 1 : 0);  // pps_loop_filter_across_slices_enabled_flag
     bw.put_bit(c.deblock ? 0 : 1);  // deblocking_filter_control_present_flag
     if (!c.deblock) {
       bw.put_bit(0);  // deblocking_filter_override_enabled_flag
@@ -204,13 +205,21 @@ std::vector<uint8_t> hevc_parameter_sets(const HevcConfig& c) {
 
 namespace {
 
-// 7.3.6.1 slice_segment_header up to slice_qp_delta (the entry points follow the CTU coding)
-void slice_header(BitWriter& bw, const HevcConfig& c, const HevcFrameParams& fp) {
+// 7.3.6.1 slice_segment_header of slice `sidx` of the picture, up to
+// slice_loop_filter_across_slices_enabled_flag (the entry points follow the CTU coding)
+void slice_header(BitWriter& bw, const HevcConfig& c, const HevcFrameParams& fp, int sidx) {
   // 7.3.6.1 slice_segment_header
   const bool idr = fp.idr != 0;
-  bw.put_bit(1);              // first_slice_segment_in_pic_flag
+  bw.put_bit(sidx == 0);      // first_slice_segment_in_pic_flag
   if (idr) bw.put_bit(0);     // no_output_of_prior_pics_flag
   bw.put_ue(0);               // slice_pic_parameter_set_id
+  if (sidx > 0) {
+    // slice_segment_address: the slice's first CTU, in Ceil(Log2(PicSizeInCtbsY)) bits
+    const int nctu = c.wctu() * c.hctu();
+    int len = 0;
+    while ((1 << len) < nctu) ++len;
+    bw.put(slice_first_row(sidx, c.slices, c.hctu()) * c.wctu(), len);
+  }
   bw.put_ue(fp.slice_type);   // slice_type
   const bool inter = fp.slice_type != 2, bslice = fp.slice_type == 0;
   if (bslice && fp.ref_poc[1] < 0) throw std::runtime_error("HEVC: a B slice needs ref_poc[1]");
@@ -339,6 +348,8 @@ void slice_header(BitWriter& bw, const HevcConfig& c, const HevcFrameParams& fp)
     bw.put_ue(5 - c.max_merge);  // five_minus_max_num_merge_cand
   }
   bw.put_se(fp.qp - 26);      // slice_qp_delta (init_qp 26)
+  // present with pps_loop_filter_across_slices_enabled_flag when SAO or deblocking is on
+  if (c.slices > 1 && (c.sao || c.deblock)) bw.put_bit(1);  // slice_loop_filter_across_slices_enabled_flag
 }
 
 // per-8x8-granule state of one picture's coded CUs (hevc_ctu_coder.h CoderState)
@@ -354,44 +365,61 @@ struct PicState {
   }
 };
 
-// entry points (WPP), byte_alignment(), the substreams, and the NAL around the RBSP
-std::vector<uint8_t> finish_slice(BitWriter& bw, const HevcConfig& c, const HevcFrameParams& fp,
-                                  const uint8_t* const* sub, const uint32_t* sizes, int nsub) {
-  if (c.wpp) {
-    if (nsub != c.hctu()) throw std::runtime_error("HEVC: one substream per CTU row with WPP");
-    // entry points count emulation prevention bytes (7.4.7.1): every substream ends in a
-    // non-zero byte, so its escaped size does not depend on its neighbours
-    std::vector<uint32_t> esc(nsub);
-    for (int r = 0; r < nsub; ++r) {
-      uint32_t extra = 0;
-      int zeros = 0;
-      for (uint32_t i = 0; i < sizes[r]; ++i) {
-        const uint8_t v = sub[r][i];
-        if (zeros >= 2 && v <= 3) {
-          ++extra;
-          zeros = 0;
-        }
-        zeros = v == 0 ? zeros + 1 : 0;
-      }
-      esc[r] = sizes[r] + extra;
-    }
-    bw.put_ue(nsub - 1);  // num_entry_point_offsets
-    if (nsub > 1) {
-      uint32_t mx = 1;
-      for (int r = 0; r + 1 < nsub; ++r) mx = std::max(mx, esc[r]);
-      int len = 1;
-      while (len < 32 && (static_cast<uint64_t>(mx - 1) >> len) != 0) ++len;
-      bw.put_ue(len - 1);  // offset_len_minus1
-      for (int r = 0; r + 1 < nsub; ++r) bw.put(esc[r] - 1, len);  // entry_point_offset_minus1
-    }
-  } else if (nsub != 1) {
-    throw std::runtime_error("HEVC: one substream per slice without WPP");
-  }
-  bw.put_bit(1);  // byte_alignment()
-  bw.align_zero();
-  for (int r = 0; r < nsub; ++r) bw.append_bytes(sub[r], sizes[r]);
+void check_slices(const HevcConfig& c) {
+  if (c.slices < 1 || c.slices > std::min(kMaxSlices, c.hctu()))
+    throw std::runtime_error("HEVC: slices in 1..min(16, CTU rows)");
+}
+
+// substreams a picture's slice data is coded in: one per CTU row with WPP, else one per slice
+int num_substreams(const HevcConfig& c) { return c.wpp ? c.hctu() : c.slices; }
+
+// One NAL per slice, in address order: the slice header, the entry points of the slice's own
+// rows (WPP), byte_alignment(), the slice's substreams, and the NAL around the RBSP
+std::vector<uint8_t> finish_slices(const HevcConfig& c, const HevcFrameParams& fp, const uint8_t* const* sub,
+                                   const uint32_t* sizes, int nsub) {
+  check_slices(c);
+  if (nsub != num_substreams(c))
+    throw std::runtime_error(c.wpp ? "HEVC: one substream per CTU row with WPP" : "HEVC: one substream per slice without WPP");
   std::vector<uint8_t> out;
-  append_hevc_nal(out, fp.idr ? NAL_IDR_W_RADL : (fp.nal_ref ? NAL_TRAIL_R : NAL_TRAIL_N), bw.bytes());
+  for (int s = 0; s < c.slices; ++s) {
+    BitWriter bw;
+    slice_header(bw, c, fp, s);
+    // substreams [q0, q1) belong to this slice
+    const int q0 = c.wpp ? slice_first_row(s, c.slices, c.hctu()) : s;
+    const int q1 = c.wpp ? slice_first_row(s + 1, c.slices, c.hctu()) : s + 1;
+    if (c.wpp) {
+      // entry points count emulation prevention bytes (7.4.7.1): every substream ends in a
+      // non-zero byte, so its escaped size does not depend on its neighbours
+      const int n = q1 - q0;
+      std::vector<uint32_t> esc(n);
+      for (int r = 0; r < n; ++r) {
+        uint32_t extra = 0;
+        int zeros = 0;
+        for (uint32_t i = 0; i < sizes[q0 + r]; ++i) {
+          const uint8_t v = sub[q0 + r][i];
+          if (zeros >= 2 && v <= 3) {
+            ++extra;
+            zeros = 0;
+          }
+          zeros = v == 0 ? zeros + 1 : 0;
+        }
+        esc[r] = sizes[q0 + r] + extra;
+      }
+      bw.put_ue(n - 1);  // num_entry_point_offsets
+      if (n > 1) {
+        uint32_t mx = 1;
+        for (int r = 0; r + 1 < n; ++r) mx = std::max(mx, esc[r]);
+        int len = 1;
+        while (len < 32 && (static_cast<uint64_t>(mx - 1) >> len) != 0) ++len;
+        bw.put_ue(len - 1);  // offset_len_minus1
+        for (int r = 0; r + 1 < n; ++r) bw.put(esc[r] - 1, len);  // entry_point_offset_minus1
+      }
+    }
+    bw.put_bit(1);  // byte_alignment()
+    bw.align_zero();
+    for (int r = q0; r < q1; ++r) bw.append_bytes(sub[r], sizes[r]);
+    append_hevc_nal(out, fp.idr ? NAL_IDR_W_RADL : (fp.nal_ref ? NAL_TRAIL_R : NAL_TRAIL_N), bw.bytes());
+  }
   return out;
 }
 
@@ -415,6 +443,7 @@ CoderPic hevc_coder_pic(const HevcConfig& c, const HevcFrameParams& fp) {
   p.tu_inter_depth = c.tu_inter_depth;
   p.sdh = c.sdh;
   p.wpp = c.wpp;
+  p.slices = c.slices;
   p.slice_type = fp.slice_type;
   p.qp = fp.qp;
   p.poc = fp.poc;
@@ -434,21 +463,18 @@ CoderPic hevc_coder_pic(const HevcConfig& c, const HevcFrameParams& fp) {
 
 std::vector<uint8_t> hevc_assemble_slice(const HevcConfig& c, const HevcFrameParams& fp, const uint8_t* const* sub,
                                          const uint32_t* sizes, int nsub) {
-  BitWriter bw;
-  slice_header(bw, c, fp);
-  return finish_slice(bw, c, fp, sub, sizes, nsub);
+  return finish_slices(c, fp, sub, sizes, nsub);
 }
 
 std::vector<uint8_t> hevc_write_slice(const HevcConfig& c, const HevcFrameParams& fp, const CtuInfo* ctu,
                                       const CuInfo* cu, const int16_t* coef_y, const int16_t* coef_cb,
                                       const int16_t* coef_cr, HevcSliceStats* stats, const PackedLevels* packed,
                                       std::vector<std::vector<uint8_t>>* substreams) {
-  BitWriter bw;
-  slice_header(bw, c, fp);
+  check_slices(c);
   // CTUs (64x64 with ctu64, else the 32x32 record blocks themselves): one substream per CTU
   // row with WPP (7.3.8.1, 9.3.1, 9.3.2.4: each row's contexts synchronised from the row
-  // above after its second CTU; rows coded by `threads` host threads with a 2-CTU lag), else
-  // one for the slice
+  // above after its second CTU unless the row starts a slice; rows coded by `threads` host
+  // threads with a 2-CTU lag), else one per slice
   const CoderPic P = hevc_coder_pic(c, fp);
   const int wctu = P.wctu, hctu = P.hctu;
   PicState ps(static_cast<size_t>(P.W / 8) * (P.H / 8));
@@ -465,7 +491,7 @@ std::vector<uint8_t> hevc_write_slice(const HevcConfig& c, const HevcFrameParams
     lv.plane[2] = coef_cr;
   }
   const CuInfo* col = (fp.col.set && c.tmvp && fp.slice_type != 2) ? fp.col.cu : nullptr;
-  const int nsub = c.wpp ? hctu : 1;
+  const int nsub = num_substreams(c);
   std::vector<BitWriter> sub(nsub);
   std::vector<std::array<CtxState, kNumCtx>> saved(hctu);
   std::vector<HevcSliceStats> rst(nsub);
@@ -485,12 +511,14 @@ std::vector<uint8_t> hevc_write_slice(const HevcConfig& c, const HevcFrameParams
     CtxState ctx[kNumCtx];
     w.begin(&P, ctu, cu, col, lv, cs, ctx, &sub[s]);
     for (int ry = r0; ry < r1; ++ry) {
-      if (c.wpp && ry > 0 && wctu >= 2) {  // 9.3.2.4 sync from CTU (1, ry-1)
+      // a slice's first row starts from the initial contexts and waits for nothing
+      const bool dep = c.wpp && !row_starts_slice(ry, c.slices, hctu);
+      if (dep && wctu >= 2) {  // 9.3.2.4 sync from CTU (1, ry-1)
         wait_for(ry - 1, 2);
         std::copy(saved[ry - 1].begin(), saved[ry - 1].end(), ctx);
       }
       for (int rx = 0; rx < wctu; ++rx) {
-        if (c.wpp && ry > 0) wait_for(ry - 1, std::min(rx + 2, wctu));
+        if (dep) wait_for(ry - 1, std::min(rx + 2, wctu));
         w.code_ctu(rx, ry);
         if (w.err) throw std::runtime_error(coder_error_text(w.err));
         if (rx == 1) std::copy(ctx, ctx + kNumCtx, saved[ry].begin());
@@ -507,8 +535,9 @@ std::vector<uint8_t> hevc_write_slice(const HevcConfig& c, const HevcFrameParams
   const int T = c.wpp ? std::max(1, std::min(c.threads, hctu)) : 1;
   auto worker = [&](int t) {
     try {
-      if (!c.wpp) {
-        code_rows(0, hctu, 0);
+      if (!c.wpp) {  // a coder per slice
+        for (int s = 0; s < c.slices; ++s)
+          code_rows(slice_first_row(s, c.slices, hctu), slice_first_row(s + 1, c.slices, hctu), s);
         return;
       }
       for (int ry = t; ry < hctu; ry += T) {
@@ -542,7 +571,7 @@ std::vector<uint8_t> hevc_write_slice(const HevcConfig& c, const HevcFrameParams
   }
   if (substreams)  // the slice data as coded, before the entry points (tests of hevc_assemble_slice)
     for (int r = 0; r < nsub; ++r) substreams->push_back(sub[r].bytes());
-  std::vector<uint8_t> out = finish_slice(bw, c, fp, ptrs.data(), sizes.data(), nsub);
+  std::vector<uint8_t> out = finish_slices(c, fp, ptrs.data(), sizes.data(), nsub);
   if (stats) {
     *stats = total;
     stats->bytes = out.size();

@@ -135,7 +135,8 @@ int mivc_launch_scale(const void* in, int w, int h, long long in_stride, long lo
 void mivc_launch_hevc_intra(int B, int W, int H, const uint16_t* sy, const uint16_t* su, const uint16_t* sv,
                             uint16_t* ry, uint16_t* ru, uint16_t* rv, void* ctu, void* cu, int16_t* cy, int16_t* cu_,
                             int16_t* cv, const int* qp, const int8_t* run, int* cand, int bd, int analyze, int recon,
-                            int* err, int sdh, const uint8_t* ctb_mask, void* stream, int ctu64, int rdoq, int rdoq_lam);
+                            int* err, int sdh, const uint8_t* ctb_mask, void* stream, int ctu64, int rdoq, int rdoq_lam,
+                            int slices);
 void mivc_launch_hevc_inter(int B, int W, int H, const uint16_t* sy, const uint16_t* su, const uint16_t* sv,
                             const uint16_t* fy, const uint16_t* fu, const uint16_t* fv, uint16_t* ry, uint16_t* ru,
                             uint16_t* rv, void* ctu, void* cu, int16_t* cy, int16_t* cu_, int16_t* cv, const int* qp,
@@ -159,7 +160,7 @@ void mivc_launch_hevc_b(int mode, int B, int wmb, int hmb, const uint8_t* src_y,
                         const int16_t* mvb_in, const uint8_t* dir_in, int16_t* mvb_out, uint8_t* dir_out, int* cost,
                         int* bits, const int* qp, const int8_t* aq, void* stream, int bslice, int max_merge, int ctu64, const uint8_t* chg_in, uint8_t* chg_out,
                         int nref0, const uint8_t* const* xref, const uint8_t* const* xhp, const int16_t* xmv,
-                        const int* xcost, const int16_t* xpm);
+                        const int* xcost, const int16_t* xpm, int slices);
 void mivc_launch_hevc_deblock(int B, int W, int H, int bd, uint16_t* y, uint16_t* u, uint16_t* v, const void* cu,
                               const void* ctu, const int8_t* run, void* stream);
 void mivc_launch_hevc_aq(int B, int W, int H, int bd, const uint16_t* sy, const uint16_t* su, const uint16_t* sv,
@@ -170,14 +171,14 @@ void mivc_launch_hevc_pack_levels(int B, int W, int H, const int16_t* cy, const 
                                   int* err, void* stream);
 void mivc_launch_hevc_merge_refine(int B, int wmb, int hmb, const uint8_t* src_y, const uint8_t* ref, const uint8_t* hp,
                                    const int16_t* mv_in, int16_t* mv_out, int* cost, const int16_t* pm, const int* qp,
-                                   const int8_t* aq, void* stream);
+                                   const int8_t* aq, void* stream, int ctu64, int slices);
 void mivc_launch_hevc_aq_terms(int B, int W, int H, int bd, const uint16_t* sy, const uint16_t* su, const uint16_t* sv,
                                float* terms, void* stream);
 void mivc_launch_hevc_aq_auto_finish(int B, int W, int H, const float* terms, const int* qp, int mode, float strength,
                                      const float* extra, long long extra_stride, int extra_rows, int* ctb_qp,
                                      int8_t* mb_aq, void* stream);
 void mivc_launch_hevc_qp_fixup(int B, int W, int H, void* ctu, const void* cu, const int* qp, const int8_t* run,
-                               int wpp, void* stream, int ctu64);
+                               int wpp, void* stream, int ctu64, int slices);
 void mivc_launch_hevc_sao(int B, int W, int H, int bd, const uint16_t* dy, const uint16_t* du, const uint16_t* dv,
                           uint16_t* y, uint16_t* u, uint16_t* v, const uint16_t* sy, const uint16_t* su,
                           const uint16_t* sv, void* ctu, const int* qp, const int8_t* run, int enable, void* stream, int ctu64);
@@ -611,17 +612,19 @@ PYBIND11_MODULE(_hip, m) {
   m.def("hevc_intra", [](int B, int W, int H, uintptr_t sy, uintptr_t su, uintptr_t sv, uintptr_t ry, uintptr_t ru,
                          uintptr_t rv, uintptr_t ctu, uintptr_t cu, uintptr_t cy, uintptr_t cu_, uintptr_t cv,
                          uintptr_t qp, uintptr_t run, uintptr_t cand, int bd, int analyze, int recon, uintptr_t err,
-                         uintptr_t stream, int sdh, uintptr_t ctb_mask, int ctu64, int rdoq, int rdoq_lam) {
+                         uintptr_t stream, int sdh, uintptr_t ctb_mask, int ctu64, int rdoq, int rdoq_lam, int slices) {
     if (rdoq < 0 || rdoq > 2 || rdoq_lam < 0 || rdoq_lam > 1472) throw std::invalid_argument("hevc_intra: rdoq in 0..2, rdoq_lam in 0..1472");
+    if (slices < 1 || slices > 16 || slices > (H / 32 + (ctu64 ? 1 : 0)) >> (ctu64 ? 1 : 0))
+      throw std::invalid_argument("hevc_intra: slices in 1..min(16, CTU rows)");
     mivc_launch_hevc_intra(B, W, H, P<uint16_t>(sy), P<uint16_t>(su), P<uint16_t>(sv), P<uint16_t>(ry), P<uint16_t>(ru),
                            P<uint16_t>(rv), P<void>(ctu), P<void>(cu), P<int16_t>(cy), P<int16_t>(cu_), P<int16_t>(cv),
                            P<int>(qp), P<int8_t>(run), P<int>(cand), bd, analyze, recon, P<int>(err), sdh,
-                           P<uint8_t>(ctb_mask), S(stream), ctu64, rdoq, rdoq_lam);
+                           P<uint8_t>(ctb_mask), S(stream), ctu64, rdoq, rdoq_lam, slices);
   }, py::arg("B"), py::arg("W"), py::arg("H"), py::arg("sy"), py::arg("su"), py::arg("sv"), py::arg("ry"), py::arg("ru"),
      py::arg("rv"), py::arg("ctu"), py::arg("cu"), py::arg("cy"), py::arg("cu_"), py::arg("cv"), py::arg("qp"),
      py::arg("run"), py::arg("cand"), py::arg("bd"), py::arg("analyze"), py::arg("recon"), py::arg("err"),
      py::arg("stream"), py::arg("sdh") = 0, py::arg("ctb_mask") = 0, py::arg("ctu64") = 0, py::arg("rdoq") = 0,
-     py::arg("rdoq_lam") = 0);
+     py::arg("rdoq_lam") = 0, py::arg("slices") = 1);
   m.def("hevc_inter", [](int B, int W, int H, uintptr_t sy, uintptr_t su, uintptr_t sv, uintptr_t fy, uintptr_t fu,
                          uintptr_t fv, uintptr_t ry, uintptr_t ru, uintptr_t rv, uintptr_t ctu, uintptr_t cu, uintptr_t cy,
                          uintptr_t cu_, uintptr_t cv, uintptr_t qp, uintptr_t run, uintptr_t cand, uintptr_t mv,
@@ -698,7 +701,7 @@ PYBIND11_MODULE(_hip, m) {
                      uintptr_t dir_out, uintptr_t cost, uintptr_t bits, uintptr_t qp, uintptr_t aq, uintptr_t stream,
                      int bslice, int max_merge, int ctu64, uintptr_t chg_in, uintptr_t chg_out, int nref0,
                      std::vector<uintptr_t> xref, std::vector<uintptr_t> xhp, uintptr_t xmv, uintptr_t xcost,
-                     uintptr_t xpm) {
+                     uintptr_t xpm, int slices) {
     // nref0 > 1 (P pictures, x265 --ref): xref / xhp = RefPicList0[1 ..] proxies and planes; the
     // P init pass also needs the farther searches xmv / xcost / xpm
     if (nref0 < 1 || nref0 > 4) throw std::invalid_argument("hevc_b: nref0 in 1..4");
@@ -725,19 +728,21 @@ PYBIND11_MODULE(_hip, m) {
     if (mode == 1 && (!mvb_in || !dir_in || mvb_in == mvb_out || dir_in == dir_out))
       throw std::invalid_argument("hevc_b: a merge pass reads and writes different motion buffers");
     if (tdir && !tmv) throw std::invalid_argument("hevc_b: tdir needs tmv");
+    if (slices < 1 || slices > 16 || slices > (hmb + (ctu64 ? 3 : 1)) >> (ctu64 ? 2 : 1))
+      throw std::invalid_argument("hevc_b: slices in 1..min(16, CTU rows)");
     mivc_launch_hevc_b(mode, B, wmb, hmb, P<uint8_t>(src), P<uint8_t>(ref0), P<uint8_t>(ref1), P<uint8_t>(hp0),
                        P<uint8_t>(hp1), P<int16_t>(mv0), P<int16_t>(mv1), P<int>(cost0), P<int>(cost1), P<int16_t>(pm0),
                        P<int16_t>(pm1), P<int16_t>(tmv), P<uint8_t>(tdir), P<int16_t>(mvb_in), P<uint8_t>(dir_in),
                        P<int16_t>(mvb_out), P<uint8_t>(dir_out), P<int>(cost), P<int>(bits), P<int>(qp), P<int8_t>(aq),
                        S(stream), bslice, max_merge, ctu64, P<uint8_t>(chg_in), P<uint8_t>(chg_out), nref0,
-                       xr, xh, P<int16_t>(xmv), P<int>(xcost), P<int16_t>(xpm));
+                       xr, xh, P<int16_t>(xmv), P<int>(xcost), P<int16_t>(xpm), slices);
   }, py::arg("mode"), py::arg("B"), py::arg("wmb"), py::arg("hmb"), py::arg("src"), py::arg("ref0"), py::arg("ref1"),
      py::arg("hp0"), py::arg("hp1"), py::arg("mv0"), py::arg("mv1"), py::arg("cost0"), py::arg("cost1"), py::arg("pm0"),
      py::arg("pm1"), py::arg("tmv"), py::arg("tdir"), py::arg("mvb_in"), py::arg("dir_in"), py::arg("mvb_out"),
      py::arg("dir_out"), py::arg("cost"), py::arg("bits"), py::arg("qp"), py::arg("aq"), py::arg("stream"),
      py::arg("bslice") = 1, py::arg("max_merge") = 5, py::arg("ctu64") = 0, py::arg("chg_in") = 0, py::arg("chg_out") = 0,
      py::arg("nref0") = 1, py::arg("xref") = std::vector<uintptr_t>{}, py::arg("xhp") = std::vector<uintptr_t>{},
-     py::arg("xmv") = 0, py::arg("xcost") = 0, py::arg("xpm") = 0);
+     py::arg("xmv") = 0, py::arg("xcost") = 0, py::arg("xpm") = 0, py::arg("slices") = 1);
   m.def("hevc_deblock", [](int B, int W, int H, int bd, uintptr_t y, uintptr_t u, uintptr_t v, uintptr_t cu,
                            uintptr_t ctu, uintptr_t run, uintptr_t stream) {
     mivc_launch_hevc_deblock(B, W, H, bd, P<uint16_t>(y), P<uint16_t>(u), P<uint16_t>(v), P<void>(cu), P<void>(ctu),
@@ -785,12 +790,17 @@ PYBIND11_MODULE(_hip, m) {
   });
   m.def("hevc_merge_refine", [](int B, int wmb, int hmb, uintptr_t src, uintptr_t ref, uintptr_t hp, uintptr_t mv_in,
                                 uintptr_t mv_out, uintptr_t cost, uintptr_t pm, uintptr_t qp, uintptr_t aq,
-                                uintptr_t stream) {
+                                uintptr_t stream, int ctu64, int slices) {
     if (mv_in == mv_out) throw std::invalid_argument("hevc_merge_refine: mv_in and mv_out must differ (Jacobi pass)");
+    if (slices < 1 || slices > 16 || slices > (hmb + (ctu64 ? 3 : 1)) >> (ctu64 ? 2 : 1))
+      throw std::invalid_argument("hevc_merge_refine: slices in 1..min(16, CTU rows)");
     if (!hp) throw std::invalid_argument("hevc_merge_refine: needs the half-sample planes");
     mivc_launch_hevc_merge_refine(B, wmb, hmb, P<uint8_t>(src), P<uint8_t>(ref), P<uint8_t>(hp), P<int16_t>(mv_in),
-                                  P<int16_t>(mv_out), P<int>(cost), P<int16_t>(pm), P<int>(qp), P<int8_t>(aq), S(stream));
-  });
+                                  P<int16_t>(mv_out), P<int>(cost), P<int16_t>(pm), P<int>(qp), P<int8_t>(aq), S(stream),
+                                  ctu64, slices);
+  }, py::arg("B"), py::arg("wmb"), py::arg("hmb"), py::arg("src"), py::arg("ref"), py::arg("hp"), py::arg("mv_in"),
+     py::arg("mv_out"), py::arg("cost"), py::arg("pm"), py::arg("qp"), py::arg("aq"), py::arg("stream"),
+     py::arg("ctu64") = 0, py::arg("slices") = 1);
   m.def("hevc_entropy_state_bytes", [](int W, int H) { return mivc_hevc_entropy_state_bytes(W, H); });
   // GPU CABAC slice data of B pictures of one coding step (kernels/hevc_entropy.hip); `pic` is
   // the step's hevc::CoderPic (host module hevc_coder_pic), substreams packed into pinned `dst`
@@ -815,10 +825,13 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("sizes"), py::arg("errs"), py::arg("offs"), py::arg("offs_host"), py::arg("dst"), py::arg("dst_cap"),
      py::arg("overflow"), py::arg("stream"), py::arg("prof") = 0, py::arg("gprog") = 0, py::arg("gctx") = 0);
   m.def("hevc_qp_fixup", [](int B, int W, int H, uintptr_t ctu, uintptr_t cu, uintptr_t qp, uintptr_t run, int wpp,
-                            uintptr_t stream, int ctu64) {
-    mivc_launch_hevc_qp_fixup(B, W, H, P<void>(ctu), P<void>(cu), P<int>(qp), P<int8_t>(run), wpp, S(stream), ctu64);
+                            uintptr_t stream, int ctu64, int slices) {
+    if (slices < 1 || slices > 16 || slices > (H / 32 + (ctu64 ? 1 : 0)) >> (ctu64 ? 1 : 0))
+      throw std::invalid_argument("hevc_qp_fixup: slices in 1..min(16, CTU rows)");
+    mivc_launch_hevc_qp_fixup(B, W, H, P<void>(ctu), P<void>(cu), P<int>(qp), P<int8_t>(run), wpp, S(stream), ctu64,
+                              slices);
   }, py::arg("B"), py::arg("W"), py::arg("H"), py::arg("ctu"), py::arg("cu"), py::arg("qp"), py::arg("run"),
-     py::arg("wpp"), py::arg("stream"), py::arg("ctu64") = 0);
+     py::arg("wpp"), py::arg("stream"), py::arg("ctu64") = 0, py::arg("slices") = 1);
   m.def("hevc_sao", [](int B, int W, int H, int bd, uintptr_t dy, uintptr_t du, uintptr_t dv, uintptr_t y, uintptr_t u,
                        uintptr_t v, uintptr_t sy, uintptr_t su, uintptr_t sv, uintptr_t ctu, uintptr_t qp, uintptr_t run,
                        int enable, uintptr_t stream, int ctu64) {

@@ -7,12 +7,13 @@
 // lanes of one wavefront would serialise them.  The rows advance as a wavefront: in each round
 // a row codes its next CTU x when the row above has coded CTU x + 1 (the above-right
 // neighbour), and row r starts with the contexts row r - 1 saved after its CTU 1 (9.3.2.4).
+// A row that starts a slice (CoderPic::slices > 1) takes fresh contexts and waits for nothing.
 // Barriers between the rounds order the rows' writes to the picture state (global) and the
-// contexts / progress (LDS).  Without WPP lane 0 of wave 0 codes the slice alone.  Each lane writes its substream to its own
-// bounded region; hevc_entropy_scan / _gather then pack the substreams into pinned host memory
-// at 16-byte aligned offsets, so only the coded bytes cross to the host, where
-// hevc_assemble_slice (hevc_writer.cc) adds the slice header, entry points and emulation
-// prevention.
+// contexts / progress (LDS).  Without WPP there is one substream per slice: lane 0 of wave
+// s mod nwave codes slice s alone.  Each lane writes its substream to its own bounded region;
+// hevc_entropy_scan / _gather then pack the substreams into pinned host memory at 16-byte
+// aligned offsets, so only the coded bytes cross to the host, where hevc_assemble_slice
+// (hevc_writer.cc) adds the slice headers, entry points and emulation prevention.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -169,13 +170,15 @@ __global__ __launch_bounds__(1024) void hevc_entropy(HevcEntropyArgs a) {
     a.sizes[o] = sink.n;
     a.errs[o] = w.err ? w.err : (sink.n > a.cap ? static_cast<int>(hevc::CE_OVERFLOW) : 0);
   };
-  if (!sP.wpp) {  // one substream: lane 0 of wave 0 codes the slice
-    sink = DevSink{nullptr, a.cap, 0, 0, 0};
-    if (tid == 0) {
-      start_row(0);
-      for (int i = 0; i < wctu * hctu; ++i) w.code_ctu(i % wctu, i / wctu);
-      end_row(0);
-    }
+  const int ns = sP.slices;
+  if (!sP.wpp) {  // one substream per slice: lane 0 of wave s mod nwave codes slice s
+    if (lead)
+      for (int s = wave; s < a.nsub; s += nwave) {
+        start_row(s);
+        const int r0 = hevc::slice_first_row(s, ns, hctu), r1 = hevc::slice_first_row(s + 1, ns, hctu);
+        for (int i = r0 * wctu; i < r1 * wctu; ++i) w.code_ctu(i % wctu, i / wctu);
+        end_row(s);
+      }
     return;
   }
   // this wave's staging area: the current CTU's records and its first kStageBlocks non-zero
@@ -222,6 +225,7 @@ __global__ __launch_bounds__(1024) void hevc_entropy(HevcEntropyArgs a) {
     // workgroup kk codes the contiguous rows [kk R, (kk + 1) R), its waves round-robin: every
     // row waits only on rows of its own workgroup or of workgroup kk - 1 (a lower blockIdx,
     // dispatched first), so progress never depends on a workgroup that is not yet resident
+    // (a row that starts a slice waits on no row at all)
     const int R = (a.nsub + a.K - 1) / a.K;
     const int r_end = min(a.nsub, (kk + 1) * R);
     int* prog = a.gprog + static_cast<size_t>(b) * a.nsub;
@@ -233,8 +237,9 @@ __global__ __launch_bounds__(1024) void hevc_entropy(HevcEntropyArgs a) {
         w.begin(&sP, ctu, cu, col, lv, cs, ctx, &sink, s_step, s_scans, s_sig);
       }
       bool timeout = false;
+      const bool dep = !hevc::row_starts_slice(r, ns, hctu);  // depends on the row above
       for (int x = 0; x < wctu && !timeout; ++x) {
-        if (r > 0) {
+        if (dep) {
           const int target = min(x + 2, wctu);
           int spins = 0;
           while (__hip_atomic_load(prog + r - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
@@ -249,7 +254,7 @@ __global__ __launch_bounds__(1024) void hevc_entropy(HevcEntropyArgs a) {
         }
         stage(x, r);
         if (lead) {
-          if (x == 0 && r > 0 && wctu >= 2)  // sync from CTU (1, r - 1)
+          if (x == 0 && dep && wctu >= 2)  // sync from CTU (1, r - 1)
             for (int i = 0; i < hevc::kNumCtx; ++i) ctx[i] = gctx[static_cast<size_t>(r - 1) * hevc::kNumCtx + i];
           w.lv.levels = &s_lv[wave][0];
           w.lv.nblocks = kStageBlocks;
@@ -288,10 +293,11 @@ __global__ __launch_bounds__(1024) void hevc_entropy(HevcEntropyArgs a) {
     // Every lane of a wave follows its row (wave-uniform control), lane 0 codes.
     if (!__syncthreads_or(lead && row < a.nsub)) break;
     int x = 0;
-    bool ready = false;
+    bool ready = false, dep = false;
     if (row < a.nsub) {
       x = s_prog[row];
-      ready = row == 0 || s_prog[row - 1] >= min(x + 2, wctu);  // above-right CTU coded (9.3.2.4: CTU 1)
+      dep = !hevc::row_starts_slice(row, ns, hctu);  // depends on the row above
+      ready = !dep || s_prog[row - 1] >= min(x + 2, wctu);  // above-right CTU coded (9.3.2.4: CTU 1)
     }
     __syncthreads();  // every wave has read the progress before any wave advances it
     if (a.prof) t_wait += __builtin_readcyclecounter() - tw;
@@ -299,7 +305,7 @@ __global__ __launch_bounds__(1024) void hevc_entropy(HevcEntropyArgs a) {
       stage(x, row);
       if (lead) {
         CtxState* ctx = s_ctx + static_cast<size_t>(wave) * hevc::kNumCtx;
-        if (x == 0 && row > 0 && wctu >= 2) {  // sync from CTU (1, row - 1)
+        if (x == 0 && dep && wctu >= 2) {  // sync from CTU (1, row - 1)
           const CtxState* src = s_ctx + static_cast<size_t>(nwave + row - 1) * hevc::kNumCtx;
           for (int i = 0; i < hevc::kNumCtx; ++i) ctx[i] = src[i];
         }
@@ -398,7 +404,9 @@ extern "C" int mivc_launch_hevc_entropy(const void* pic, int B, const int* qp, c
   HevcEntropyArgs a{};
   a.prof = prof;
   a.pic = *static_cast<const CoderPic*>(pic);
-  const int nsub = a.pic.wpp ? a.pic.hctu : 1;
+  const int ns = a.pic.slices;
+  if (ns < 1 || ns > mivc::hevc::kMaxSlices || ns > a.pic.hctu) return -1;
+  const int nsub = a.pic.wpp ? a.pic.hctu : ns;  // a substream per CTU row, else per slice
   if (nsub < 1 || nsub > 100 || (cap & 15) || a.pic.W % 32 || a.pic.H % 32 ||
       state_bytes < entropy_state_bytes(a.pic.W, a.pic.H))
     return -1;

@@ -844,7 +844,8 @@ __global__ __launch_bounds__(kAqFinishThreads) void hevc_aq_auto_finish(int W, i
 // the start of the slice and, with WPP, of every CTB row); the CTB's delta is coded in
 // its first CU with a coded residual, earlier CUs keep the prediction, and a CTB
 // without any coded residual takes the prediction as its QpY.  Deblocking and the
-// CABAC writer read the result.  One thread per CTB row (WPP) or per slot.
+// CABAC writer read the result.  One thread per CTU row (WPP) or per slice (hevc_tables.h
+// slice_of_row: without WPP the prediction restarts at each slice's first CTU).
 //
 // 64x64 CTUs (ctu64): the 32x32 record blocks are the quantization groups (diff_cu_qp_delta_depth
 // 1) of a CTU, coded in z-order; a group's prediction averages the QpY left of and above it
@@ -854,7 +855,8 @@ __device__ __forceinline__ int qg_granule_qp(const CtuInfo& t, int z) { return z
 
 __global__ __launch_bounds__(256) void hevc_qp_fixup(int wctb, int hctb, CtuInfo* __restrict__ ctu,
                                                      const CuInfo* __restrict__ cu, const int* __restrict__ qp,
-                                                     const int8_t* __restrict__ run, int wpp, int ctu64) {
+                                                     const int8_t* __restrict__ run, int wpp, int ctu64,
+                                                     int slices) {
   const int slot = blockIdx.x;
   if (run[slot] == 0) return;
   const int nctb = wctb * hctb;
@@ -871,10 +873,11 @@ __global__ __launch_bounds__(256) void hevc_qp_fixup(int wctb, int hctb, CtuInfo
   };
   if (ctu64) {
     const int wctu = (wctb + 1) / 2, hctu = (hctb + 1) / 2;
-    const int rows_per = wpp ? 1 : hctu;
-    for (int r0 = threadIdx.x * rows_per; r0 < hctu; r0 += blockDim.x * rows_per) {
+    for (int u = threadIdx.x; u < (wpp ? hctu : slices); u += blockDim.x) {
+      const int r0 = wpp ? u : hevc::slice_first_row(u, slices, hctu);
+      const int r1 = wpp ? u + 1 : hevc::slice_first_row(u + 1, slices, hctu);
       int prev = qp[slot];
-      for (int r = r0; r < r0 + rows_per; ++r)
+      for (int r = r0; r < r1; ++r)
         for (int x = 0; x < wctu; ++x)
           for (int q = 0; q < 4; ++q) {
             const int bx = 2 * x + (q & 1), by = 2 * r + (q >> 1);
@@ -894,10 +897,11 @@ __global__ __launch_bounds__(256) void hevc_qp_fixup(int wctb, int hctb, CtuInfo
     }
     return;
   }
-  const int rows_per = wpp ? 1 : hctb;
-  for (int r0 = threadIdx.x * rows_per; r0 < hctb; r0 += blockDim.x * rows_per) {
+  for (int u = threadIdx.x; u < (wpp ? hctb : slices); u += blockDim.x) {
+    const int r0 = wpp ? u : hevc::slice_first_row(u, slices, hctb);
+    const int r1 = wpp ? u + 1 : hevc::slice_first_row(u + 1, slices, hctb);
     int prev = qp[slot];
-    for (int r = r0; r < r0 + rows_per; ++r)
+    for (int r = r0; r < r1; ++r)
       for (int x = 0; x < wctb; ++x) {
         const size_t c = static_cast<size_t>(slot) * nctb + r * wctb + x;
         const int first = first_coded(c);
@@ -1114,9 +1118,9 @@ extern "C" void mivc_launch_hevc_aq_auto_finish(int B, int W, int H, const float
 }
 
 extern "C" void mivc_launch_hevc_qp_fixup(int B, int W, int H, void* ctu, const void* cu, const int* qp,
-                                          const int8_t* run, int wpp, void* stream, int ctu64) {
+                                          const int8_t* run, int wpp, void* stream, int ctu64, int slices) {
   hipLaunchKernelGGL(hevc_qp_fixup, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream), W / 32, H / 32,
-                     static_cast<CtuInfo*>(ctu), static_cast<const CuInfo*>(cu), qp, run, wpp, ctu64);
+                     static_cast<CtuInfo*>(ctu), static_cast<const CuInfo*>(cu), qp, run, wpp, ctu64, slices);
 }
 
 // levels of B slots -> packed form: nzmap [B, nctb, 2] u64, off [B, nctb] u32, out: B slots of

@@ -40,6 +40,7 @@ struct HevcIntraArgs {
   const uint8_t* ctb_mask;                // [B, nctb] analyse only where nonzero (P pictures: the CTBs
                                           // where intra may beat the motion search); null = every CTB
   int ctu64;                              // 64x64 CTUs: the 32x32 blocks are coded in z-order inside them
+  int slices;                             // independent slices of whole CTU rows (hevc_tables.h slice_of_row)
 };
 
 constexpr int kNoIntra = 1 << 26;  // candidate cost of a CTB the analysis skipped (inter decisive)
@@ -47,15 +48,24 @@ constexpr int kNoIntra = 1 << 26;  // candidate cost of a CTB the analysis skipp
 // luma neighbour (xr, yr) of a position relative to the 32x32 block (rx, ry): z-scan
 // availability (6.4.1) at the 4x4 minimum-TB granularity; zcur = z-order index (zorder4) of
 // the current block's first 4x4 block.  32x32 CTBs: blocks in raster order; 64x64 CTUs
-// (ctu64): CTUs in raster order, their four blocks in z-order.
-__device__ __forceinline__ bool nb_avail(int xr, int yr, int zcur, int rx, int ry, int wctb, int hctb, int ctu64) {
+// (ctu64): CTUs in raster order, their four blocks in z-order.  top = first block row of the
+// current block's slice (slice_top): the blocks above it belong to another slice.
+__device__ __forceinline__ bool nb_avail(int xr, int yr, int zcur, int rx, int ry, int wctb, int hctb, int ctu64,
+                                         int top) {
   const int tx = rx + (xr >> 5), ty = ry + (yr >> 5);
-  if (tx < 0 || ty < 0 || tx >= wctb || ty >= hctb) return false;
+  if (tx < 0 || ty < top || tx >= wctb || ty >= hctb) return false;
   if (tx == rx && ty == ry) return zorder4((xr & 31) >> 2, (yr & 31) >> 2) < zcur;
   if (!ctu64) return ty < ry || (ty == ry && tx < rx);
   const int ux = tx >> 1, uy = ty >> 1, cx = rx >> 1, cy = ry >> 1;
   if (ux != cx || uy != cy) return uy < cy || (uy == cy && ux < cx);
   return ((tx & 1) | ((ty & 1) << 1)) < ((rx & 1) | ((ry & 1) << 1));
+}
+
+// first 32x32 block row of the slice that holds block row ry (0 with one slice per picture)
+__device__ __forceinline__ int slice_top(int ry, int hctb, int ctu64, int slices) {
+  if (slices <= 1) return 0;
+  const int c64 = ctu64 ? 1 : 0, hu = (hctb + c64) >> c64;
+  return hevc::slice_first_row(hevc::slice_of_row(ry >> c64, slices, hu), slices, hu) << c64;
 }
 
 __device__ __forceinline__ void ref_pos(int i, int n, int cx, int cy, int* x, int* y) {
@@ -173,6 +183,7 @@ __global__ __launch_bounds__(256, 4) void hevc_intra_analyze(HevcIntraArgs a) {
   const int X0 = rx * 32, Y0 = ry * 32;
   const int tid = threadIdx.x;
   const int bd = a.bd, maxv = (1 << bd) - 1;
+  const int top = slice_top(ry, g.hctb, a.ctu64, a.slices);
   const uint16_t* src = a.src_y + slot * g.ysize();
   for (int i = tid; i < 65 * 65; i += 256) {
     const int y = i / 65 - 1, x = i % 65 - 1;
@@ -195,7 +206,7 @@ __global__ __launch_bounds__(256, 4) void hevc_intra_analyze(HevcIntraArgs a) {
     for (int i = 0; i < E; ++i) {
       int x, y;
       ref_pos(i, n, cx, cy, &x, &y);
-      if (nb_avail(x, y, zc, rx, ry, g.wctb, g.hctb, a.ctu64)) {
+      if (nb_avail(x, y, zc, rx, ry, g.wctb, g.hctb, a.ctu64, top)) {
         p[i] = S.ext[(y + 1) * 65 + x + 1];
         if (first < 0) first = i;
       } else {
@@ -232,7 +243,7 @@ __global__ __launch_bounds__(256, 4) void hevc_intra_analyze(HevcIntraArgs a) {
     for (int i = 0; i < 17; ++i) {
       int x, y;
       ref_pos(i, 4, px, py, &x, &y);
-      if (nb_avail(x, y, pu, rx, ry, g.wctb, g.hctb, a.ctu64)) {
+      if (nb_avail(x, y, pu, rx, ry, g.wctb, g.hctb, a.ctu64, top)) {
         p[i] = S.ext[(y + 1) * 65 + x + 1];
         if (first < 0) first = i;
       } else {
@@ -524,11 +535,12 @@ __device__ __forceinline__ bool recon_block(const HevcIntraArgs& a, ReconShared&
   const int stride = LUMA ? RT : CT2;
   uint16_t* tile = LUMA ? S.rt : S.rc[comp - 1];
   // 1. reference samples (availability from the luma granule of each sample)
+  const int top = slice_top(ry, g.hctb, a.ctu64, a.slices);
   hv::build_refs(S.p, n, bd,
                  [&](int i) {
                    int x, y;
                    ref_pos(i, n, cx, cy, &x, &y);
-                   return nb_avail(x << sc, y << sc, zc, rx, ry, g.wctb, g.hctb, a.ctu64);
+                   return nb_avail(x << sc, y << sc, zc, rx, ry, g.wctb, g.hctb, a.ctu64, top);
                  },
                  [&](int i) {
                    int x, y;
@@ -690,7 +702,9 @@ __global__ __launch_bounds__(64 * kHevcIntraWaves) void hevc_intra_recon(HevcInt
   __shared__ hv::DctLds D;
   __shared__ int prog[kMaxRows];
   const HevcGeom& g = a.g;
-  const int slot = blockIdx.x, comp = blockIdx.y;
+  // one workgroup per (slot, component, slice): slices share no dependency, so each runs the
+  // wavefront over its own rows with the progress in its own LDS
+  const int slot = blockIdx.x, comp = blockIdx.y, sl = blockIdx.z;
   const int run = a.run[slot];
   if (run == 0) return;
   hv::dct_lds_init(D);
@@ -706,15 +720,17 @@ __global__ __launch_bounds__(64 * kHevcIntraWaves) void hevc_intra_recon(HevcInt
   // CTBs, or (ctu64) 64x64 CTUs whose four 32x32 blocks follow in z-order
   const int c64 = a.ctu64 ? 1 : 0;
   const int wu = (g.wctb + c64) >> c64, hu = (g.hctb + c64) >> c64, nq = c64 ? 4 : 1;
+  // this slice's unit rows [y0, y1): the first waits for no row above
+  const int y0 = hevc::slice_first_row(sl, a.slices, hu), y1 = hevc::slice_first_row(sl + 1, a.slices, hu);
   // a block's "has intra CUs" flag (P pictures): any of its 16 granule records is intra
   auto block_work = [&](int bx, int by) {
     const size_t cb = (static_cast<size_t>(slot) * g.nctb() + by * g.wctb + bx) * 16;
     return __ballot(lane_id() < 16 && a.cu[cb + lane_id()].pred == hevc::CU_INTRA) != 0;
   };
-  for (int y = w; y < hu; y += kHevcIntraWaves) {
+  for (int y = y0 + w; y < y1; y += kHevcIntraWaves) {
     if (run == 1) {  // I picture: every unit
       for (int x = 0; x < wu; ++x) {
-        if (y > 0) row_wait(prog, y - 1, min(x + 2, wu), a.err);
+        if (y > y0) row_wait(prog, y - 1, min(x + 2, wu), a.err);
         for (int q = 0; q < nq; ++q) {
           const int bx = (x << c64) + (q & 1), by = (y << c64) + (q >> 1);
           if (bx >= g.wctb || by >= g.hctb) continue;
@@ -742,7 +758,7 @@ __global__ __launch_bounds__(64 * kHevcIntraWaves) void hevc_intra_recon(HevcInt
         const int x = x0 + __builtin_ctzll(mask);
         mask &= mask - 1;
         if (x > 0) row_publish(prog, y, x);  // the units before x in this row are final
-        if (y > 0) row_wait(prog, y - 1, min(x + 2, wu), a.err);
+        if (y > y0) row_wait(prog, y - 1, min(x + 2, wu), a.err);
         for (int q = 0; q < nq; ++q) {
           const int bx = (x << c64) + (q & 1), by = (y << c64) + (q >> 1);
           if (bx >= g.wctb || by >= g.hctb) continue;
@@ -793,6 +809,7 @@ static HevcIntraArgs make_intra_args(int B, int W, int H, const uint16_t* sy, co
   a.nxn_in_p = 0;
   a.ctb_mask = nullptr;
   a.ctu64 = 0;
+  a.slices = 1;
   return a;
 }
 
@@ -800,14 +817,15 @@ extern "C" void mivc_launch_hevc_intra(int B, int W, int H, const uint16_t* sy, 
                                        uint16_t* ry, uint16_t* ru, uint16_t* rv, void* ctu, void* cu, int16_t* cy,
                                        int16_t* cu_, int16_t* cv, const int* qp, const int8_t* run, int* cand, int bd,
                                        int analyze, int recon, int* err, int sdh, const uint8_t* ctb_mask,
-                                       void* stream, int ctu64, int rdoq, int rdoq_lam) {
+                                       void* stream, int ctu64, int rdoq, int rdoq_lam, int slices) {
   HevcIntraArgs a = make_intra_args(B, W, H, sy, su, sv, ry, ru, rv, ctu, cu, cy, cu_, cv, qp, run, cand, bd, err, sdh);
   a.ctb_mask = ctb_mask;
   a.ctu64 = ctu64;
   a.rdoq = rdoq;
   a.rdoq_lam = rdoq_lam;
+  a.slices = slices;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (analyze) hipLaunchKernelGGL(hevc_intra_analyze, dim3(a.g.nctb(), B), dim3(256), 0, s, a);
-  if (recon && rdoq) hipLaunchKernelGGL(hevc_intra_recon<true>, dim3(B, 3), dim3(64 * kHevcIntraWaves), 0, s, a);
-  else if (recon) hipLaunchKernelGGL(hevc_intra_recon<false>, dim3(B, 3), dim3(64 * kHevcIntraWaves), 0, s, a);
+  if (recon && rdoq) hipLaunchKernelGGL(hevc_intra_recon<true>, dim3(B, 3, slices), dim3(64 * kHevcIntraWaves), 0, s, a);
+  else if (recon) hipLaunchKernelGGL(hevc_intra_recon<false>, dim3(B, 3, slices), dim3(64 * kHevcIntraWaves), 0, s, a);
 }

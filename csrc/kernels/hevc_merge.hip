@@ -6,6 +6,7 @@
 #include "kcommon.h"
 #include "mb_row.h"
 #include "qpel.h"
+#include "../common/hevc_tables.h"
 
 namespace mivc {
 namespace gpu {
@@ -17,6 +18,16 @@ namespace gpu {
 // the search's SATD + lambda * mvd bits, so the CABAC writer can code the CU as merge / skip.
 // Jacobi pass: reads mv_in, writes mv_out.  (The candidates approximate the normative merge
 // list on the 16x16 grid; the writer codes AMVP whenever the vector is not in the real list.)
+// With several slices per picture a slice's first block row has no neighbours above.
+
+// first 16x16 block row of the slice that holds block row my (sh = log2(CTU size / 16); slices
+// are whole CTU rows, hevc_tables.h slice_of_row)
+__device__ __forceinline__ int slice_top16(const Geom& g, int sh, int slices, int my) {
+  if (slices <= 1) return 0;
+  const int hu = (g.hmb + (1 << sh) - 1) >> sh;
+  return hevc::slice_first_row(hevc::slice_of_row(my >> sh, slices, hu), slices, hu) << sh;
+}
+
 struct MergeRefineArgs {
   Geom g;
   const uint8_t* src_y;
@@ -28,6 +39,8 @@ struct MergeRefineArgs {
   const int16_t* pm;        // [B, nmb, 2] the ME's predictor (to recover the SATD part of cost)
   const int* qp;
   const int8_t* aq;
+  int ctu_shift;            // log2(CTU size / 16): 1 for 32x32 CTBs, 2 for 64x64 CTUs
+  int slices;               // slices per picture
 };
 
 __global__ __launch_bounds__(64) void hevc_merge_refine(MergeRefineArgs a) {
@@ -48,11 +61,12 @@ __global__ __launch_bounds__(64) void hevc_merge_refine(MergeRefineArgs a) {
     ky[nk] = vy;
     ++nk;
   };
+  const int top = slice_top16(g, a.ctu_shift, a.slices, my);  // the slice's first block row
   add(mx > 0, mb - 1);                              // A1
-  add(my > 0, mb - g.wmb);                          // B1
-  add(my > 0 && mx < g.wmb - 1, mb - g.wmb + 1);    // B0
+  add(my > top, mb - g.wmb);                        // B1
+  add(my > top && mx < g.wmb - 1, mb - g.wmb + 1);  // B0
   add(mx > 0 && my < g.hmb - 1, mb + g.wmb - 1);    // A0
-  add(mx > 0 && my > 0, mb - g.wmb - 1);            // B2
+  add(mx > 0 && my > top, mb - g.wmb - 1);          // B2
   {
     bool z = false;
     for (int j = 0; j < nk; ++j) z |= kx[j] == 0 && ky[j] == 0;
@@ -125,6 +139,7 @@ struct HevcBArgs {
   int bslice;                   // 0: P picture (list 0 only)
   int max_merge;                // MaxNumMergeCand
   int ctu_shift;                // log2(CTU size / 16): 1 for 32x32 CTBs, 2 for 64x64 CTUs
+  int slices;                   // slices per picture: a slice's first block row has no neighbours above
   // merge passes: blocks whose motion the previous pass changed (nullable: every block is
   // re-evaluated); a block whose own and whose neighbours' motion stayed put would rebuild the
   // same list at the same costs, so it only copies its motion through
@@ -154,9 +169,10 @@ __device__ __forceinline__ const uint8_t* l0_hp(const HevcBArgs& a, int r) {
 __device__ __forceinline__ int ref_bins(int r, int nref) { return nref <= 1 ? 0 : min(r + 1, nref - 1); }
 
 // z-scan availability (6.4.1) of the 16x16 block (nx, ny) for the block (mx, my) on the 16x16
-// grid: CTUs in raster order, blocks inside a CTU in z-order
-__device__ __forceinline__ bool avail16(const Geom& g, int sh, int nx, int ny, int mx, int my) {
-  if (nx < 0 || ny < 0 || nx >= g.wmb || ny >= g.hmb) return false;
+// grid: CTUs in raster order, blocks inside a CTU in z-order; top = first block row of the
+// current block's slice (slice_top16)
+__device__ __forceinline__ bool avail16(const Geom& g, int sh, int nx, int ny, int mx, int my, int top) {
+  if (nx < 0 || ny < top || nx >= g.wmb || ny >= g.hmb) return false;
   const int ux = nx >> sh, uy = ny >> sh, cx = mx >> sh, cy = my >> sh;
   if (ux != cx || uy != cy) return uy < cy || (uy == cy && ux < cx);
   const int m = (1 << sh) - 1;
@@ -281,11 +297,13 @@ __global__ __launch_bounds__(64) void hevc_b_merge(HevcBArgs a) {
     return da == db && wa[0] == wb[0] && wa[1] == wb[1] && wa[2] == wb[2] && wa[3] == wb[3];
   };
   int dA1 = 0, dB1 = 0, dB0 = 0, dA0 = 0, dB2 = 0, wA1[4], wB1[4], wB0[4], wA0[4], wB2[4];
-  const bool a1 = mx > 0, av_b1 = my > 0;
+  const int top = slice_top16(g, a.ctu_shift, a.slices, my);
+  const bool a1 = mx > 0, av_b1 = my > top;
   // above-right / below-left: z-scan order inside the CTU (32x32: B0 unavailable for quadrant 3,
   // A0 available for quadrant 0 only)
-  bool b0 = avail16(g, a.ctu_shift, mx + 1, my - 1, mx, my), a0 = avail16(g, a.ctu_shift, mx - 1, my + 1, mx, my);
-  bool b2 = mx > 0 && my > 0;
+  bool b0 = avail16(g, a.ctu_shift, mx + 1, my - 1, mx, my, top);
+  bool a0 = avail16(g, a.ctu_shift, mx - 1, my + 1, mx, my, top);
+  bool b2 = mx > 0 && my > top;
   if (a1) load(mb - 1, &dA1, wA1);
   if (av_b1) load(mb - g.wmb, &dB1, wB1);
   if (b0) load(mb - g.wmb + 1, &dB0, wB0);
@@ -414,8 +432,11 @@ using namespace mivc::gpu;
 
 extern "C" void mivc_launch_hevc_merge_refine(int B, int wmb, int hmb, const uint8_t* src_y, const uint8_t* ref,
                                               const uint8_t* hp, const int16_t* mv_in, int16_t* mv_out, int* cost,
-                                              const int16_t* pm, const int* qp, const int8_t* aq, void* stream) {
+                                              const int16_t* pm, const int* qp, const int8_t* aq, void* stream,
+                                              int ctu64, int slices) {
   MergeRefineArgs a;
+  a.ctu_shift = ctu64 ? 2 : 1;
+  a.slices = slices;
   a.g = Geom{B, wmb, hmb, wmb * 16, hmb * 16};
   a.src_y = src_y;
   a.ref = ref;
@@ -438,8 +459,9 @@ extern "C" void mivc_launch_hevc_b(int mode, int B, int wmb, int hmb, const uint
                                    const int* qp, const int8_t* aq, void* stream, int bslice, int max_merge,
                                    int ctu64, const uint8_t* chg_in, uint8_t* chg_out, int nref0,
                                    const uint8_t* const* xref, const uint8_t* const* xhp, const int16_t* xmv,
-                                   const int* xcost, const int16_t* xpm) {
+                                   const int* xcost, const int16_t* xpm, int slices) {
   HevcBArgs a;
+  a.slices = slices;
   a.nref0 = nref0 < 1 ? 1 : nref0;
   for (int r = 0; r < 3; ++r) {
     a.xref[r] = r + 1 < a.nref0 ? xref[r] : ref0;

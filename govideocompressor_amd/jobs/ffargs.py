@@ -216,6 +216,7 @@ H264_PARAMS = {
     "weightb": ("weightb", _flag),
     "no-weightb": ("weightb", lambda v: not _flag(v)),
     "trellis": ("trellis", lambda v: 2 if _int_in(0, 2)(v) > 0 else 0),
+    "slices": ("slices", _int_in(0, 16)),  # 0: the encoder's automatic choice
     # direct=spatial: decided in an MB wavefront (h264_b.hip b_spatial_decide), -1.9 % BD-rate
     # and ~26 % fewer frames/s than temporal on the benchmark content (profiles/r3_direct_rd.md)
     "direct": ("direct", _only("temporal", "spatial")),
@@ -258,6 +259,7 @@ HEVC_PARAMS = {
     "no-deblock": ("deblock", lambda v: not _flag(v)),
     "ctu": ("ctu64", lambda v: {"32": False, "64": True}[v] if v in ("32", "64") else _only("32 or 64")(v)),
     "ref": ("@ref", _int_in(1, 1)),
+    "slices": ("slices", _int_in(1, 16)),
     "crf": ("@crf", _float_in(0.0, 51.0)),
     "qp": ("@qp", _int_in(0, 51)),
     "pools": ("@threads", str),

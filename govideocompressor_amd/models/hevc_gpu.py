@@ -207,6 +207,32 @@ class HevcParams:
     inter8: bool = True
     inter8_overhead: int = 16
     inter8_min_satd: int = 1000
+    # x265 --slices: independent slices per picture, each a run of whole CTU rows (CTU row r is in
+    # slice r * slices // rows), one NAL each: nothing is predicted across a slice edge (intra
+    # samples, merge / AMVP candidates, contexts, the QP predictor), deblocking and SAO still
+    # filter across it.  The closed-loop intra reconstruction runs one workgroup per slice, the
+    # entropy coders start a slice's first row without waiting, and a decoder may parse the
+    # slices in parallel.  The motion search's own predictor still reads across slice edges
+    # (cost only).  1 <= slices <= min(16, CTU rows); measurements: profiles/hevc_slices.md --
+    # opt-in, in no preset
+    slices: int = 1
+
+    def ctu_rows(self) -> int:
+        """CTU rows of the coded picture (64-sample rows with ctu64, else 32-sample rows)."""
+        return -(-int(self.height) // (64 if self.ctu64 else 32))
+
+    def check_slices(self) -> None:
+        s = self.slices
+        if isinstance(s, bool) or not isinstance(s, int) or not 1 <= s <= min(16, self.ctu_rows()):
+            raise ValueError(f"slices must be in 1..min(16, CTU rows = {self.ctu_rows()})")
+
+    def describe(self) -> str:
+        """The encoder's tag string: codec, size, rate mode and the opt-in tools that are on."""
+        rate = f"crf{self.crf:g}" if self.crf is not None else f"qp{self.qp}"
+        tag = f"hevc {self.width}x{self.height} {rate} ctu{64 if self.ctu64 else 32}"
+        if self.slices > 1:
+            tag += f" slices{self.slices}"
+        return tag
 
     def eff_refs(self) -> int:
         """Active list-0 pictures of P pictures (1 for intra-only and keyint GOPs)."""
@@ -236,7 +262,7 @@ class HevcParams:
                     cu_qp_delta=int(self.adaptive_qp()), tu_inter_depth=int(self.tu_inter_depth), sdh=int(self.sdh),
                     level_idc=int(self.level_idc), bframes=self.eff_bframes(), tmvp=int(self.tmvp and not self.intra_only),
                     pyramid=int(self.pyramid), ctu64=int(self.ctu64), weightp=int(self.eff_weightp()),
-                    weightb=int(self.eff_weightb()), refs=self.eff_refs())
+                    weightb=int(self.eff_weightb()), refs=self.eff_refs(), slices=int(self.slices))
 
     def frame_qps(self) -> tuple[int, int]:
         qp_p = int(round(self.crf)) if self.crf is not None else int(self.qp)
@@ -312,6 +338,7 @@ class GpuHevcEncoder:
             raise ValueError("rdoq_lambda must be in (0, 4]")
         if not 0.0 < float(params.rd_cbf_lambda) <= 4.0:
             raise ValueError("rd_cbf_lambda must be in (0, 4]")
+        params.check_slices()
         self.p = params
         self.B = int(slots)
         d = torch.device(device)
@@ -481,19 +508,19 @@ class GpuHevcEncoder:
 
     def _alloc_entropy(self) -> None:
         """Device buffers of the GPU entropy stage: per-picture coder state, one bounded region
-        per substream (WPP: one per CTU row) and the collocated pictures' records per DPB slot;
+        per substream (WPP: one per CTU row, else one per slice) and the collocated pictures' records per DPB slot;
         the packed substreams go to pinned host sets (:meth:`_entropy_host`)."""
         dev, B = self.dev, self.B
         W, H = self.W, self.H
         ctu_log2 = 6 if self.p.ctu64 else 5
         wctu, hctu = -(-W // (1 << ctu_log2)), -(-H // (1 << ctu_log2))
-        self.ent_nsub = hctu if self.p.wpp else 1
+        self.ent_nsub = hctu if self.p.wpp else int(self.p.slices)
         if self.ent_nsub > 100:
             raise ValueError("GPU entropy: at most 100 CTU rows (use entropy='host')")
         # bytes per substream: 12 KiB per CTU of a row (about 2 bytes per 4:2:0 sample of a
-        # 64x64 CTU), the whole picture without WPP
+        # 64x64 CTU), the rows of the largest slice without WPP
         per_ctu = 12288 if self.p.ctu64 else 3072
-        self.ent_cap = ((per_ctu * wctu * (1 if self.p.wpp else hctu)) + 15) // 16 * 16
+        self.ent_cap = ((per_ctu * wctu * (1 if self.p.wpp else -(-hctu // int(self.p.slices)))) + 15) // 16 * 16
         self.ent_state_bytes = int(self.hip.hevc_entropy_state_bytes(W, H))
         self.ent_state = torch.empty((B, self.ent_state_bytes), dtype=torch.uint8, device=dev)
         # one substream area per pinned host set: a step whose slice data outgrows the pinned
@@ -1017,6 +1044,7 @@ class GpuHevcEncoder:
             # RDOQ of the reconstruction launches: lam = round(rdoq_lambda * kRdoqLamScale)
             rdoq = dict(rdoq=int(self.p.rdoq_level), rdoq_lam=int(round(float(self.p.rdoq_lambda) * 368))) \
                 if self.p.rdoq_level else {}
+            ns = int(self.p.slices)  # slices per picture (HevcParams.slices)
             intra_args = (B, self.W, self.H, p(self.src[0]), p(self.src[1]), p(self.src[2]), p(cur[0]), p(cur[1]),
                           p(cur[2]), p(self.ctu), p(self.cu), p(self.coef[0]), p(self.coef[1]), p(self.coef[2]),
                           p(self.ctb_qp), p(self.run), p(self.cand), bd)
@@ -1024,7 +1052,8 @@ class GpuHevcEncoder:
                 self.run.fill_(1)
                 self.prev_mv.zero_()  # no motion predictors across a closed GOP (or from an earlier call)
                 with st("intra_i"):
-                    self.hip.hevc_intra(*intra_args, 1, 1, p(self.err), s, int(self.p.sdh), 0, int(self.p.ctu64), **rdoq)
+                    self.hip.hevc_intra(*intra_args, 1, 1, p(self.err), s, int(self.p.sdh), 0, int(self.p.ctu64), slices=ns,
+                                        **rdoq)
             else:
                 self.run.fill_(2)
                 ref8, hp = self.ref8s[r0], self.me_hps[r0]
@@ -1071,13 +1100,14 @@ class GpuHevcEncoder:
                             xs = dict(xmv=p(self.xmv), xcost=p(self.xcost), xpm=p(self.xpm)) if far else {}
                             self.hip.hevc_b(2, *pargs, p(self.mv), 0, p(self.me_cost), 0, p(self.prev_mv), 0, 0, 0, 0, 0,
                                             p(self.mvb[0]), p(self.dirb[0]), p(self.bcost), p(self.bbits), p(self.qp),
-                                            p(self.mb_aq), s, 0, int(self.p.max_merge), int(self.p.ctu64), **far, **xs)
+                                            p(self.mb_aq), s, 0, int(self.p.max_merge), int(self.p.ctu64), slices=ns,
+                                            **far, **xs)
                             for it in range(int(self.p.merge_refine)):
                                 i_, o_ = it % 2, (it + 1) % 2
                                 self.hip.hevc_b(1, *pargs, 0, 0, 0, 0, 0, 0, tm_, td_, p(self.mvb[i_]), p(self.dirb[i_]),
                                                 p(self.mvb[o_]), p(self.dirb[o_]), p(self.bcost), p(self.bbits),
                                                 p(self.qp), p(self.mb_aq), s, 0, int(self.p.max_merge), int(self.p.ctu64),
-                                                *self._chg_args(it), **far)
+                                                *self._chg_args(it), slices=ns, **far)
                             fin = int(self.p.merge_refine) % 2
                             self.me_cost.copy_(self.bcost)
                             self.mv.copy_(self.mvb[fin][..., 0:2])
@@ -1100,7 +1130,7 @@ class GpuHevcEncoder:
                                 a_, b_ = (self.mv, self.mv_tmp) if it % 2 == 0 else (self.mv_tmp, self.mv)
                                 self.hip.hevc_merge_refine(B, self.wmb, self.hmb, s8, p(ref8), p(hp), p(a_),
                                                            p(b_), p(self.me_cost), p(self.prev_mv), p(self.qp),
-                                                           p(self.mb_aq), s)
+                                                           p(self.mb_aq), s, int(self.p.ctu64), ns)
                             if int(self.p.merge_refine) % 2:
                                 self.mv.copy_(self.mv_tmp)
                 else:
@@ -1126,14 +1156,15 @@ class GpuHevcEncoder:
                         bargs = (B, self.wmb, self.hmb, p(self.src8), p(ref8), p(ref8b), p(hp), p(hpb))
                         self.hip.hevc_b(0, *bargs, p(self.mv), p(self.mv1), p(self.me_cost), p(self.me_cost1),
                                         p(self.pm0), p(self.pm1), 0, 0, 0, 0, p(self.mvb[0]), p(self.dirb[0]),
-                                        p(self.bcost), p(self.bbits), p(self.qp), p(self.mb_aq), s, 1, int(self.p.max_merge), int(self.p.ctu64))
+                                        p(self.bcost), p(self.bbits), p(self.qp), p(self.mb_aq), s, 1, int(self.p.max_merge),
+                                        int(self.p.ctu64), slices=ns)
                         tm_, td_ = (p(self.tmv), p(self.tdir)) if tmvp else (0, 0)
                         for it in range(int(self.p.merge_refine)):
                             i_, o_ = it % 2, (it + 1) % 2
                             self.hip.hevc_b(1, *bargs, 0, 0, 0, 0, 0, 0, tm_, td_, p(self.mvb[i_]), p(self.dirb[i_]),
                                             p(self.mvb[o_]), p(self.dirb[o_]), p(self.bcost), p(self.bbits), p(self.qp),
                                             p(self.mb_aq), s, 1, int(self.p.max_merge), int(self.p.ctu64),
-                                            *self._chg_args(it))
+                                            *self._chg_args(it), slices=ns)
                         fin = int(self.p.merge_refine) % 2
                         self.me_cost.copy_(self.bcost)
                     r1p = self.rec[r1]
@@ -1147,7 +1178,8 @@ class GpuHevcEncoder:
                     mask = p(self._intra_gate()) if self.p.intra_gate else 0
                     if mask:
                         gate_sum.append(self.ctb_need.sum(dtype=torch.int64))
-                    self.hip.hevc_intra(*intra_args, 1, 0, p(self.err), s, int(self.p.sdh), mask, int(self.p.ctu64))
+                    self.hip.hevc_intra(*intra_args, 1, 0, p(self.err), s, int(self.p.sdh), mask, int(self.p.ctu64),
+                                        slices=ns)
                 with st("inter"):
                     self.hip.hevc_inter(B, self.W, self.H, p(self.src[0]), p(self.src[1]), p(self.src[2]), p(ref[0]),
                                         p(ref[1]), p(ref[2]), p(cur[0]), p(cur[1]), p(cur[2]), p(self.ctu), p(self.cu),
@@ -1156,11 +1188,11 @@ class GpuHevcEncoder:
                                         int(self.p.sdh), int(self.p.intra_bias_p), **inter_kw, **rdoq, **self.rd_cbf_kw)
                 with st("intra_recon"):
                     self.hip.hevc_intra(*intra_args, 0, 1, p(self.err), s, int(self.p.sdh), 0,
-                                        int(self.p.ctu64), **rdoq)   # intra CUs, wavefront
+                                        int(self.p.ctu64), slices=ns, **rdoq)   # intra CUs, wavefront
                 if pic.kind == "P":
                     self.prev_mv.copy_(self.mv)
             self.hip.hevc_qp_fixup(B, self.W, self.H, p(self.ctu), p(self.cu), p(self.qp), p(self.run), int(self.p.wpp), s,
-                                   int(self.p.ctu64))
+                                   int(self.p.ctu64), ns)
             if self.p.deblock:
                 with st("deblock"):
                     self.hip.hevc_deblock(B, self.W, self.H, bd, p(cur[0]), p(cur[1]), p(cur[2]), p(self.cu),

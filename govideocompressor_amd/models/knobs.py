@@ -80,6 +80,7 @@ HEVC = {
     "MIVC_HEVC_RD_CBF_LAMBDA": "rd_cbf_lambda",
     "MIVC_HEVC_AQ_MODE": "aq_mode",
     "MIVC_HEVC_WEIGHTB": "weightb",
+    "MIVC_HEVC_SLICES": "slices",
 }
 # bench.py shape knobs (they change what is measured, so they also need --allow-knobs)
 # (MIVC_HIP_LIB: an alternative kernel library, tools/build_variant.py -- same-box A/B timing)

@@ -224,18 +224,19 @@ def random_gop_stream(host, width: int, height: int, frames: int, bframes: int =
 
 
 def expected_ctb_qps(ctu: np.ndarray, cy: np.ndarray, cb: np.ndarray, cr: np.ndarray, slice_qp: int,
-                     wpp: bool) -> np.ndarray:
+                     wpp: bool, slices: int = 1) -> np.ndarray:
     """QpY per CTB a decoder derives from cu_qp_delta records (8.6.1, one quantization
     group per CTB): the CTB's own QP when any block of it has a coded level, else the
-    prediction (the previous CTB's QpY; the slice QP at the slice start and, with WPP,
-    at every CTB row)."""
+    prediction (the previous CTB's QpY; the slice QP at the start of each of the ``slices``
+    slices -- CTB row r is in slice r * slices // rows -- and, with WPP, at every CTB row)."""
     H, W = cy.shape
     wc = W // CTB
+    hc = H // CTB
     out = np.zeros(len(ctu), np.int32)
     prev = slice_qp
     for i in range(len(ctu)):
         rx, ry = i % wc, i // wc
-        if wpp and rx == 0:
+        if rx == 0 and (wpp or ry == 0 or ry * slices // hc != (ry - 1) * slices // hc):
             prev = slice_qp
         X, Y = rx * CTB, ry * CTB
         coded = (cy[Y:Y + CTB, X:X + CTB].any() or cb[Y // 2:Y // 2 + 16, X // 2:X // 2 + 16].any()

@@ -148,6 +148,9 @@ HEVC_CONFIGS = {
     # x265 --aq-mode 2 / 3 (auto-variance AQ; 2 is what -tune ssim selects)
     "aq2": dict(aq_mode=2),
     "aq3": dict(aq_mode=3),
+    # x265 --slices: independent slices per picture (profiles/hevc_slices.md)
+    "slices2": dict(slices=2),
+    "slices4": dict(slices=4),
 }
 
 
