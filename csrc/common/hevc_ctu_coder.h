@@ -81,6 +81,7 @@ struct WriterCtxMap {
     run(CTX_REF_IDX, dec::C_REF_IDX, 2);
     run(CTX_CU_QP_DELTA, dec::C_QP_DELTA, 2);
     run(CTX_INTER_PRED, dec::C_INTER_PRED, 5);
+    run(CTX_TSKIP, dec::C_TSKIP, 2);
   }
 };
 static constexpr WriterCtxMap kWriterCtxMap{};
@@ -301,6 +302,8 @@ struct CoderPic {
   int col_set, col_poc, col_ref_poc[2], col_list_poc[2][4];
   // independent slices of whole CTU rows (hevc_tables.h slice_of_row); 1: the picture is one slice
   int slices;
+  // transform_skip_enabled_flag: every 4x4 TU codes transform_skip_flag (from CoderLevels::tsmap)
+  int tskip;
 };
 
 // level source: packed non-zero 4x4 blocks (levels != null), else coefficient planes;
@@ -314,6 +317,9 @@ struct CoderLevels {
   // staged per CTU (GPU): `levels` holds the first `nblocks` non-zero blocks of the current CTU
   // (its 32x32 blocks in z-order, each in packed order), the rest are read from the planes
   int stage_ctu = 0;
+  // with CoderPic::tskip: per CTB the 4x4 TUs coded with transform_skip_flag 1, laid out like
+  // nzmap (null: none); a set bit must belong to a coded 4x4 TU
+  const uint64_t* tsmap = nullptr;
 };
 
 // picture-wide state of coded CUs, one entry per 8x8 granule (mode4: per 4x4 block); shared by
@@ -344,6 +350,7 @@ enum CoderError : int {
   CE_SDH_PARITY,
   CE_OVERFLOW,
   CE_TIMEOUT,
+  CE_TSKIP_BLOCK,
   CE_COUNT
 };
 inline const char* coder_error_text(int e) {
@@ -362,6 +369,7 @@ inline const char* coder_error_text(int e) {
     case CE_SDH_PARITY: return "HEVC: sign data hiding parity does not match the hidden sign";
     case CE_OVERFLOW: return "HEVC entropy: substream buffer overflow";
     case CE_TIMEOUT: return "HEVC GPU entropy: wavefront progress timeout";
+    case CE_TSKIP_BLOCK: return "HEVC: transform skip bit on a block that is not a coded 4x4 TU";
     default: return "HEVC slice coder error";
   }
 }
@@ -497,6 +505,9 @@ struct CtuCoder {
   uint64_t nz_luma = 0;
   uint32_t nz_chroma[2] = {0, 0};
   uint32_t ctb_base = 0;
+  // transform skip bits of the current 32x32 block not yet coded (a 4x4 TU clears its own)
+  uint64_t ts_luma = 0;
+  uint32_t ts_chroma[2] = {0, 0};
   int cu64_midx = -1;
   Motion cu64_mot;
   uint64_t* prof = nullptr;  // CP_N cycle counters (diagnostics), or null
@@ -537,6 +548,8 @@ struct CtuCoder {
     nz_luma = 0;
     nz_chroma[0] = nz_chroma[1] = 0;
     ctb_base = 0;
+    ts_luma = 0;
+    ts_chroma[0] = ts_chroma[1] = 0;
     cu64_midx = -1;
     cu_stage = nullptr;
     stage_cx = stage_cy = -1;
@@ -774,6 +787,19 @@ struct CtuCoder {
     HV_LDS(sig_tab);
     HV_LDS(scans_tab);
     HV_LDS(en.out);
+    if (P->tskip && log2 == 2) {  // transform_skip_flag: the TU's bit of the map, which it takes
+      const int side = cidx ? 4 : 8, m = cidx ? 15 : 31;
+      const int bit = ((by0 & m) >> 2) * side + ((bx0 & m) >> 2);
+      int ts;
+      if (cidx == 0) {
+        ts = static_cast<int>((ts_luma >> bit) & 1u);
+        ts_luma &= ~(1ull << bit);
+      } else {
+        ts = static_cast<int>((ts_chroma[cidx - 1] >> bit) & 1u);
+        ts_chroma[cidx - 1] &= ~(1u << bit);
+      }
+      en.encode(ts, cx[CTX_TSKIP + (cidx ? 1 : 0)]);
+    }
     int lx = (sbs[last_i] & 15) * 4 + (ps[last_p] & 15), ly = (sbs[last_i] >> 4) * 4 + (ps[last_p] >> 4);
     if (scan_idx == 2) {
       const int t = lx;
@@ -898,6 +924,11 @@ struct CtuCoder {
     HV_LDS(P);
     const ProfScope prof_scope(prof, CP_SCAN);
     const size_t ci = static_cast<size_t>(y0 / kCtb) * wctb + x0 / kCtb;
+    if (P->tskip && lv.tsmap) {
+      ts_luma = lv.tsmap[2 * ci];
+      ts_chroma[0] = static_cast<uint32_t>(lv.tsmap[2 * ci + 1] & 0xFFFFu);
+      ts_chroma[1] = static_cast<uint32_t>((lv.tsmap[2 * ci + 1] >> 16) & 0xFFFFu);
+    }
     if (lv.nzmap) {
       nz_luma = lv.nzmap[2 * ci];
       nz_chroma[0] = static_cast<uint32_t>(lv.nzmap[2 * ci + 1] & 0xFFFFu);
@@ -1574,6 +1605,8 @@ struct CtuCoder {
         for (int r = 0; r < 4; ++r) write_cu(x1 + (r & 1) * 8, y1 + (r >> 1) * 8, 3, dofs + 2);
       }
     }
+    // every transform skip bit of the block was taken by a coded 4x4 TU
+    if (ts_luma || ts_chroma[0] || ts_chroma[1]) fail(CE_TSKIP_BLOCK);
     // qPY_PREV of the next quantization group: the QpY of this group's last CU
     if (P->cu_qp_delta) qp_prev = qp_coded ? qp_ctb : qp_pred_cur;
   }
@@ -1604,6 +1637,7 @@ struct CtuCoder {
       else if (!(m == m0)) return false;
       scan_ctb_nz(bx << 5, by << 5);
       if (nz_luma || nz_chroma[0] || nz_chroma[1]) return false;
+      if (ts_luma || ts_chroma[0] || ts_chroma[1]) fail(CE_TSKIP_BLOCK);
     }
     Motion ml[5];
     const int nm = merge_list(x0, y0, 64, ml);

@@ -147,7 +147,8 @@ enum Ctx : int {
   CTX_REF_IDX = 142,         // 2
   CTX_CU_QP_DELTA = 144,     // 2
   CTX_INTER_PRED = 146,      // 5 (inter_pred_idc: ctxInc = CtDepth for the first bin, 4 for the second)
-  kNumCtx = 151,
+  CTX_TSKIP = 151,           // 2 (transform_skip_flag: luma, chroma)
+  kNumCtx = 153,
 };
 
 // initValues of these contexts for the three initTypes come from the full spec table of the

@@ -371,6 +371,7 @@ hevc::HevcConfig hevc_cfg_from(const py::dict& d) {
   c.weightb = dget<int>(d, "weightb", 0);
   c.refs = dget<int>(d, "refs", 1);
   c.slices = dget<int>(d, "slices", 1);
+  c.tskip = dget<int>(d, "tskip", 0) ? 1 : 0;
   if (c.refs < 1 || c.refs > hevc::kMaxRefs) throw std::runtime_error("HEVC: refs in 1..4");
   if (c.tu_inter_depth < 0 || c.tu_inter_depth > 1) throw std::runtime_error("HEVC: tu_inter_depth in 0..1");
   if (c.threads < 1 || c.threads > 256) throw std::runtime_error("HEVC: threads in 1..256");
@@ -380,6 +381,15 @@ hevc::HevcConfig hevc_cfg_from(const py::dict& d) {
   if (c.slices < 1 || c.slices > std::min(hevc::kMaxSlices, c.hctu()))
     throw std::runtime_error("HEVC: slices in 1..min(16, CTU rows)");
   return c;
+}
+
+// optional transform skip map of `pics` pictures (hevc::PackedLevels::tsmap): None, or uint64 [pics * nctb * 2]
+const uint64_t* tsmap_from(const py::object& o, py::ssize_t need, std::vector<py::array>& keep) {
+  if (o.is_none()) return nullptr;
+  auto a = py::array_t<uint64_t, py::array::c_style>::ensure(o);
+  if (!a || a.size() < need) throw std::runtime_error("tsmap: expected uint64, two words per CTB");
+  keep.push_back(a);
+  return a.data();
 }
 
 template <class T>
@@ -412,6 +422,7 @@ py::dict hevc_picture_to_dict(const hevc::HevcPicture& p) {
   d["coef_y"] = to_array(p.coef_y, {H, W});
   d["coef_cb"] = to_array(p.coef_cb, {H / 2, W / 2});
   d["coef_cr"] = to_array(p.coef_cr, {H / 2, W / 2});
+  d["tsmap"] = to_array(p.tsmap, {static_cast<py::ssize_t>(p.tsmap.size() / 2), 2});
   return d;
 }
 
@@ -841,10 +852,12 @@ PYBIND11_MODULE(_host, m) {
       "hevc_write_slice",
       [](const py::dict& cfg, const py::dict& fp, py::array_t<uint8_t, py::array::c_style> ctu,
          py::array_t<uint8_t, py::array::c_style> cu, py::array_t<int16_t, py::array::c_style> cy,
-         py::array_t<int16_t, py::array::c_style> cb, py::array_t<int16_t, py::array::c_style> cr) {
+         py::array_t<int16_t, py::array::c_style> cb, py::array_t<int16_t, py::array::c_style> cr,
+         const py::object& tsmap) {
         hevc::HevcConfig c = hevc_cfg_from(cfg);
         const py::ssize_t nctu = static_cast<py::ssize_t>(c.wctb()) * c.hctb();
         std::vector<py::array> keep;
+        const uint64_t* ts = tsmap_from(tsmap, nctu * 2, keep);
         const hevc::HevcFrameParams f = hevc_frame_from(fp, keep, static_cast<size_t>(nctu) * hevc::kCusPerCtb * hevc::kCuInfoBytes);
         const py::ssize_t W = c.coded_width(), H = c.coded_height();
         if (ctu.size() != nctu * 32) throw std::runtime_error("ctu records: wrong size");
@@ -857,7 +870,7 @@ PYBIND11_MODULE(_host, m) {
           py::gil_scoped_release rel;
           nal = hevc::hevc_write_slice(c, f, reinterpret_cast<const hevc::CtuInfo*>(ctu.data()),
                                        reinterpret_cast<const hevc::CuInfo*>(cu.data()), cy.data(), cb.data(), cr.data(),
-                                       &st);
+                                       &st, nullptr, nullptr, ts);
         }
         py::dict stats;
         stats["bins"] = st.bins;
@@ -869,16 +882,18 @@ PYBIND11_MODULE(_host, m) {
         return py::make_tuple(to_bytes(nal), stats);
       },
       py::arg("cfg"), py::arg("frame"), py::arg("ctu"), py::arg("cu"), py::arg("coef_y"), py::arg("coef_cb"),
-      py::arg("coef_cr"));
+      py::arg("coef_cr"), py::arg("tsmap") = py::none());
   m.def(
       "hevc_write_slice_packed",
       [](const py::dict& cfg, const py::dict& fp, py::array_t<uint8_t, py::array::c_style> ctu,
          py::array_t<uint8_t, py::array::c_style> cu, py::array_t<uint64_t, py::array::c_style> nzmap,
-         py::array_t<uint32_t, py::array::c_style> ctb_off, py::array_t<int16_t, py::array::c_style> levels) {
+         py::array_t<uint32_t, py::array::c_style> ctb_off, py::array_t<int16_t, py::array::c_style> levels,
+         const py::object& tsmap) {
         // levels in the GPU encoder's packed form (hevc::PackedLevels)
         hevc::HevcConfig c = hevc_cfg_from(cfg);
         const py::ssize_t nctu = static_cast<py::ssize_t>(c.wctb()) * c.hctb();
         std::vector<py::array> keep;
+        const uint64_t* ts = tsmap_from(tsmap, nctu * 2, keep);
         const hevc::HevcFrameParams f = hevc_frame_from(fp, keep, static_cast<size_t>(nctu) * hevc::kCusPerCtb * hevc::kCuInfoBytes);
         if (ctu.size() != nctu * 32) throw std::runtime_error("ctu records: wrong size");
         if (cu.size() != nctu * hevc::kCusPerCtb * hevc::kCuInfoBytes) throw std::runtime_error("cu records: wrong size");
@@ -889,6 +904,7 @@ PYBIND11_MODULE(_host, m) {
         pk.ctb_off = ctb_off.data();
         pk.levels = levels.data();
         pk.nblocks = static_cast<size_t>(levels.size() / 16);
+        pk.tsmap = ts;
         hevc::HevcSliceStats st;
         std::vector<uint8_t> nal;
         {
@@ -903,17 +919,19 @@ PYBIND11_MODULE(_host, m) {
         return py::make_tuple(to_bytes(nal), stats);
       },
       py::arg("cfg"), py::arg("frame"), py::arg("ctu"), py::arg("cu"), py::arg("nzmap"), py::arg("ctb_off"),
-      py::arg("levels"));
+      py::arg("levels"), py::arg("tsmap") = py::none());
   m.def(
       "hevc_slice_substreams",
       [](const py::dict& cfg, const py::dict& fp, py::array_t<uint8_t, py::array::c_style> ctu,
          py::array_t<uint8_t, py::array::c_style> cu, py::array_t<int16_t, py::array::c_style> cy,
-         py::array_t<int16_t, py::array::c_style> cb, py::array_t<int16_t, py::array::c_style> cr) {
+         py::array_t<int16_t, py::array::c_style> cb, py::array_t<int16_t, py::array::c_style> cr,
+         const py::object& tsmap) {
         // the slice data substreams the host writer codes for a picture (one per CTU row with
         // WPP), for checking hevc_assemble_slices against hevc_write_slice
         hevc::HevcConfig c = hevc_cfg_from(cfg);
         const py::ssize_t nctu = static_cast<py::ssize_t>(c.wctb()) * c.hctb();
         std::vector<py::array> keep;
+        const uint64_t* ts = tsmap_from(tsmap, nctu * 2, keep);
         const hevc::HevcFrameParams f = hevc_frame_from(fp, keep, static_cast<size_t>(nctu) * hevc::kCusPerCtb * hevc::kCuInfoBytes);
         const py::ssize_t W = c.coded_width(), H = c.coded_height();
         if (ctu.size() != nctu * 32 || cu.size() != nctu * hevc::kCusPerCtb * hevc::kCuInfoBytes ||
@@ -922,13 +940,13 @@ PYBIND11_MODULE(_host, m) {
         std::vector<std::vector<uint8_t>> subs;
         hevc::hevc_write_slice(c, f, reinterpret_cast<const hevc::CtuInfo*>(ctu.data()),
                                reinterpret_cast<const hevc::CuInfo*>(cu.data()), cy.data(), cb.data(), cr.data(), nullptr,
-                               nullptr, &subs);
+                               nullptr, &subs, ts);
         py::list out;
         for (auto& v : subs) out.append(to_bytes(v));
         return out;
       },
       py::arg("cfg"), py::arg("frame"), py::arg("ctu"), py::arg("cu"), py::arg("coef_y"), py::arg("coef_cb"),
-      py::arg("coef_cr"));
+      py::arg("coef_cr"), py::arg("tsmap") = py::none());
   // slice geometry (hevc_tables.h): the slice of CTU row r, and whether row r starts a slice
   m.def("hevc_slice_of_row", [](int r, int slices, int hctu) { return hevc::slice_of_row(r, slices, hctu); });
   m.def("hevc_row_starts_slice", [](int r, int slices, int hctu) { return hevc::row_starts_slice(r, slices, hctu); });
@@ -999,7 +1017,7 @@ PYBIND11_MODULE(_host, m) {
       [](const py::dict& cfg, const py::list& frames, py::array_t<uint8_t, py::array::c_style> ctu,
          py::array_t<uint8_t, py::array::c_style> cu, py::array_t<uint64_t, py::array::c_style> nzmap,
          py::array_t<uint32_t, py::array::c_style> ctb_off, py::array_t<int16_t, py::array::c_style> levels,
-         int threads, bool with_stats) {
+         int threads, bool with_stats, const py::object& tsmap) {
         // One picture per slot of a batch step ([B, ...] arrays, frames[b] = frame params),
         // coded by `threads` native threads with the GIL released for the whole batch (a
         // Python thread per picture would queue on the GIL after every slice).
@@ -1013,6 +1031,7 @@ PYBIND11_MODULE(_host, m) {
         if (levels.ndim() != 2 || levels.shape(0) < B || levels.shape(1) % 16) throw std::runtime_error("packed levels: [B, 16 n]");
         std::vector<hevc::HevcFrameParams> fps(B);
         std::vector<py::array> keep;
+        const uint64_t* ts = tsmap_from(tsmap, B * nctu * 2, keep);
         for (py::ssize_t b = 0; b < B; ++b)
           fps[b] = hevc_frame_from(frames[b].cast<py::dict>(), keep,
                                    static_cast<size_t>(nctu) * hevc::kCusPerCtb * hevc::kCuInfoBytes);
@@ -1031,6 +1050,7 @@ PYBIND11_MODULE(_host, m) {
                 pk.ctb_off = ctb_off.data() + static_cast<size_t>(b) * nctu;
                 pk.levels = levels.data() + static_cast<size_t>(b) * per_lv;
                 pk.nblocks = per_lv / 16;
+                if (ts) pk.tsmap = ts + static_cast<size_t>(b) * nctu * 2;
                 nals[b] = hevc::hevc_write_slice(
                     c, fps[b], reinterpret_cast<const hevc::CtuInfo*>(ctu.data() + static_cast<size_t>(b) * nctu * 32),
                     reinterpret_cast<const hevc::CuInfo*>(cu.data() + static_cast<size_t>(b) * nctu * hevc::kCusPerCtb * hevc::kCuInfoBytes),
@@ -1065,7 +1085,8 @@ PYBIND11_MODULE(_host, m) {
         return out;
       },
       py::arg("cfg"), py::arg("frames"), py::arg("ctu"), py::arg("cu"), py::arg("nzmap"), py::arg("ctb_off"),
-      py::arg("levels"), py::arg("threads") = 1, py::arg("with_stats") = false);
+      py::arg("levels"), py::arg("threads") = 1, py::arg("with_stats") = false,
+      py::arg("tsmap") = py::none());
   m.def(
       "hevc_decode",
       [](py::bytes data, bool skip_filters) {

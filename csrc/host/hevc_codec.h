@@ -55,6 +55,9 @@ struct HevcConfig {
   // x265 --slices: independent slices per picture, each a run of whole CTU rows
   // (hevc_tables.h slice_of_row), one NAL each; 1 <= slices <= min(16, hctu())
   int slices = 1;
+  // x265 --tskip: transform_skip_enabled_flag; every 4x4 TU codes transform_skip_flag from the
+  // picture's tsmap (no map: every flag 0)
+  int tskip = 0;
   int ctb_log2() const { return ctu64 ? 6 : kCtbLog2; }
   int wctu() const { return (coded_width() + (1 << ctb_log2()) - 1) >> ctb_log2(); }
   int hctu() const { return (coded_height() + (1 << ctb_log2()) - 1) >> ctb_log2(); }
@@ -129,17 +132,22 @@ struct PackedLevels {
   const uint32_t* ctb_off = nullptr;
   const int16_t* levels = nullptr;
   size_t nblocks = 0;  // blocks available in `levels` (bounds check)
+  // with HevcConfig::tskip: the 4x4 TUs coded with transform_skip_flag 1, laid out like nzmap
+  // (bits of coded 4x4 TUs only); refused when the flag is off
+  const uint64_t* tsmap = nullptr;
 };
 
 // The slice NALs (Annex-B) of a whole picture: one, or HevcConfig::slices in address order;
 // the statistics are sums over them.  ctu: [wctb*hctb]; cu: [wctb*hctb*16]
 // (z-order granules); coef planes sized like the coded picture (luma) / half (chroma), or
-// null with `packed` given.
+// null with `packed` given.  tsmap: the transform skip map of a picture given as planes (as
+// PackedLevels::tsmap).
 std::vector<uint8_t> hevc_write_slice(const HevcConfig& cfg, const HevcFrameParams& fp, const CtuInfo* ctu,
                                       const CuInfo* cu, const int16_t* coef_y, const int16_t* coef_cb,
                                       const int16_t* coef_cr, HevcSliceStats* stats,
                                       const PackedLevels* packed = nullptr,
-                                      std::vector<std::vector<uint8_t>>* substreams = nullptr);
+                                      std::vector<std::vector<uint8_t>>* substreams = nullptr,
+                                      const uint64_t* tsmap = nullptr);
 
 // The slice-data coder's view of a picture (hevc_ctu_coder.h): sizes, tools, slice type, QP,
 // reference / collocated POCs (the collocated records pointer is passed separately)
@@ -161,6 +169,7 @@ struct HevcPicture {
   std::vector<CtuInfo> ctu;
   std::vector<CuInfo> cu;
   std::vector<int16_t> coef_y, coef_cb, coef_cr;
+  std::vector<uint64_t> tsmap;          // the 4x4 TUs parsed with transform_skip_flag 1 (as PackedLevels::tsmap)
 };
 
 class HevcDecoder {

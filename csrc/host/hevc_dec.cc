@@ -537,6 +537,7 @@ struct HevcStreamDecoder::Impl {
       d.coef_y.assign(n4 * 16, 0);
       d.coef_cb.assign(n4 * 4, 0);
       d.coef_cr.assign(n4 * 4, 0);
+      d.tsmap.assign(static_cast<size_t>(W / 32) * (H / 32) * 2, 0);
     }
     pic_open = true;
     return true;
@@ -1673,6 +1674,12 @@ struct HevcStreamDecoder::Impl {
       const int stride = cidx ? W / 2 : W;
       for (int y = 0; y < n; ++y)
         for (int x = 0; x < n; ++x) pl[static_cast<size_t>(y0 + y) * stride + x0 + x] = lev[y * n + x];
+      if (tskip && log2 == 2) {
+        const int m = cidx ? 15 : 31, side = cidx ? 4 : 8;
+        const size_t ci = static_cast<size_t>((y0 << (cidx ? 1 : 0)) / 32) * (W / 32) + (x0 << (cidx ? 1 : 0)) / 32;
+        const int bit = ((y0 & m) >> 2) * side + ((x0 & m) >> 2) + (cidx == 2 ? 16 : 0);
+        dp->tsmap[2 * ci + (cidx ? 1 : 0)] |= 1ull << bit;
+      }
     }
     if (intra && opt.gpu_records) push_op(x0, y0, log2, cidx, static_cast<uint8_t>(intra_mode), tu);
     if (opt.recon) {
@@ -2597,6 +2604,7 @@ void HevcDecoder::decode(const uint8_t* data, size_t n) {
     p.coef_y = std::move(s.coef_y);
     p.coef_cb = std::move(s.coef_cb);
     p.coef_cr = std::move(s.coef_cr);
+    p.tsmap = std::move(s.tsmap);
     out_.push_back(std::move(p));
   }
 }

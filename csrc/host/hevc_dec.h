@@ -141,6 +141,7 @@ struct DecPicture {
   std::vector<CtuInfo> ctu;
   std::vector<CuInfo> cu;
   std::vector<int16_t> coef_y, coef_cb, coef_cr;
+  std::vector<uint64_t> tsmap;      // parsed transform_skip_flags, laid out like PackedLevels::tsmap
 };
 
 // ScalingFactor layout: sizeId 0..3, matrixId 0..5, raster (x + y * n): 6 x (16 + 64 + 256 + 1024)

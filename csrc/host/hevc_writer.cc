@@ -173,7 +173,7 @@ std::vector<uint8_t> hevc_parameter_sets(const HevcConfig& c) {
     bw.put_ue(0);   // num_ref_idx_l1_default_active_minus1
     bw.put_se(0);   // init_qp_minus26
     bw.put_bit(0);  // constrained_intra_pred_flag
-    bw.put_bit(0);  // transform_skip_enabled_flag
+    bw.put_bit(c.tskip ? 1 : 0);  // transform_skip_enabled_flag
     bw.put_bit(c.cu_qp_delta ? 1 : 0);  // cu_qp_delta_enabled_flag
     // diff_cu_qp_delta_depth: one quantization group per 32x32 block (per CTB, or 4 per 64x64 CTU)
     if (c.cu_qp_delta) bw.put_ue(c.ctu64 ? 1 : 0);
@@ -444,6 +444,7 @@ CoderPic hevc_coder_pic(const HevcConfig& c, const HevcFrameParams& fp) {
   p.sdh = c.sdh;
   p.wpp = c.wpp;
   p.slices = c.slices;
+  p.tskip = c.tskip ? 1 : 0;
   p.slice_type = fp.slice_type;
   p.qp = fp.qp;
   p.poc = fp.poc;
@@ -469,8 +470,10 @@ std::vector<uint8_t> hevc_assemble_slice(const HevcConfig& c, const HevcFramePar
 std::vector<uint8_t> hevc_write_slice(const HevcConfig& c, const HevcFrameParams& fp, const CtuInfo* ctu,
                                       const CuInfo* cu, const int16_t* coef_y, const int16_t* coef_cb,
                                       const int16_t* coef_cr, HevcSliceStats* stats, const PackedLevels* packed,
-                                      std::vector<std::vector<uint8_t>>* substreams) {
+                                      std::vector<std::vector<uint8_t>>* substreams, const uint64_t* tsmap) {
   check_slices(c);
+  if (packed && packed->tsmap) tsmap = packed->tsmap;
+  if (tsmap && !c.tskip) throw std::runtime_error("HEVC: a transform skip map needs HevcConfig::tskip");
   // CTUs (64x64 with ctu64, else the 32x32 record blocks themselves): one substream per CTU
   // row with WPP (7.3.8.1, 9.3.1, 9.3.2.4: each row's contexts synchronised from the row
   // above after its second CTU unless the row starts a slice; rows coded by `threads` host
@@ -490,6 +493,7 @@ std::vector<uint8_t> hevc_write_slice(const HevcConfig& c, const HevcFrameParams
     lv.plane[1] = coef_cb;
     lv.plane[2] = coef_cr;
   }
+  lv.tsmap = tsmap;
   const CuInfo* col = (fp.col.set && c.tmvp && fp.slice_type != 2) ? fp.col.cu : nullptr;
   const int nsub = num_substreams(c);
   std::vector<BitWriter> sub(nsub);

@@ -22,7 +22,11 @@ int mivc_launch_hevc_entropy(const void* pic, int B, const int* qp, const void* 
                              uint8_t* state, long long state_bytes, uint8_t* out, unsigned cap, unsigned* sizes,
                              int* errs, unsigned long long* offs, unsigned long long* offs_host, uint8_t* dst,
                              unsigned long long dst_cap, int* overflow, void* stream, unsigned long long* prof,
-                             int* gprog, void* gctx);
+                             int* gprog, void* gctx, const unsigned long long* tsmap);
+long long mivc_hevc_entropy_ctx_bytes();
+int mivc_launch_hevc_tskip_probe(int nblk, const uint16_t* src, const uint16_t* pred, int16_t* lev, uint16_t* rec, int* flag,
+                                 long long* terms, int bd, int qp, int intra, int dst, int scan, int sdh, int rdoq,
+                                 int rdoq_lam, int lamq, void* stream);
 int mivc_launch_hevc_decode(const mivc::gpu::HevcDecParams* p, int stage, void* stream);
 void mivc_launch_synth(void* y, void* u, void* v, int width, int height, int slots, int frames, int frame0,
                        uint32_t seed, int bit_depth, int slot0, void* stream, int kind);
@@ -136,7 +140,7 @@ void mivc_launch_hevc_intra(int B, int W, int H, const uint16_t* sy, const uint1
                             uint16_t* ry, uint16_t* ru, uint16_t* rv, void* ctu, void* cu, int16_t* cy, int16_t* cu_,
                             int16_t* cv, const int* qp, const int8_t* run, int* cand, int bd, int analyze, int recon,
                             int* err, int sdh, const uint8_t* ctb_mask, void* stream, int ctu64, int rdoq, int rdoq_lam,
-                            int slices);
+                            int slices, unsigned long long* tsmap, const int* ts_lamq, int* ts_count);
 void mivc_launch_hevc_inter(int B, int W, int H, const uint16_t* sy, const uint16_t* su, const uint16_t* sv,
                             const uint16_t* fy, const uint16_t* fu, const uint16_t* fv, uint16_t* ry, uint16_t* ru,
                             uint16_t* rv, void* ctu, void* cu, int16_t* cy, int16_t* cu_, int16_t* cv, const int* qp,
@@ -144,7 +148,8 @@ void mivc_launch_hevc_inter(int B, int W, int H, const uint16_t* sy, const uint1
                             int tu_split, int sdh, int intra_bias, void* stream, const int16_t* mvb,
                             const uint8_t* dirb, const uint16_t* f1y, const uint16_t* f1u, const uint16_t* f1v,
                             const int16_t* wp, const uint16_t* const* xref, const int16_t* mv8, int rdoq, int rdoq_lam,
-                            const int16_t* wpb, const int* rd_lamq);
+                            const int16_t* wpb, const int* rd_lamq, unsigned long long* tsmap, const int* ts_lamq,
+                            int* ts_count);
 int mivc_launch_hevc_mc_probe(int ncase, const uint16_t* ref0, const uint16_t* ref1, int pw, int ph, const int16_t* cases,
                               uint16_t* out, int nt, int n, int dir, int bd, int ww, int wo, int ww1, int wo1, int wb,
                               int lean, void* stream);
@@ -612,26 +617,35 @@ PYBIND11_MODULE(_hip, m) {
   m.def("hevc_intra", [](int B, int W, int H, uintptr_t sy, uintptr_t su, uintptr_t sv, uintptr_t ry, uintptr_t ru,
                          uintptr_t rv, uintptr_t ctu, uintptr_t cu, uintptr_t cy, uintptr_t cu_, uintptr_t cv,
                          uintptr_t qp, uintptr_t run, uintptr_t cand, int bd, int analyze, int recon, uintptr_t err,
-                         uintptr_t stream, int sdh, uintptr_t ctb_mask, int ctu64, int rdoq, int rdoq_lam, int slices) {
+                         uintptr_t stream, int sdh, uintptr_t ctb_mask, int ctu64, int rdoq, int rdoq_lam, int slices,
+                         uintptr_t tsmap, uintptr_t ts_lamq, uintptr_t ts_count) {
+    // tsmap (uint64 [B, nctb, 2], cleared per picture), ts_lamq (int32 [52]) and ts_count (int32 [3]):
+    // the transform skip decision on 4x4 TUs (hevc_tskip.h)
+    if ((tsmap != 0) != (ts_lamq != 0) || (tsmap != 0) != (ts_count != 0))
+      throw std::invalid_argument("hevc_intra: tsmap, ts_lamq and ts_count come together");
     if (rdoq < 0 || rdoq > 2 || rdoq_lam < 0 || rdoq_lam > 1472) throw std::invalid_argument("hevc_intra: rdoq in 0..2, rdoq_lam in 0..1472");
     if (slices < 1 || slices > 16 || slices > (H / 32 + (ctu64 ? 1 : 0)) >> (ctu64 ? 1 : 0))
       throw std::invalid_argument("hevc_intra: slices in 1..min(16, CTU rows)");
     mivc_launch_hevc_intra(B, W, H, P<uint16_t>(sy), P<uint16_t>(su), P<uint16_t>(sv), P<uint16_t>(ry), P<uint16_t>(ru),
                            P<uint16_t>(rv), P<void>(ctu), P<void>(cu), P<int16_t>(cy), P<int16_t>(cu_), P<int16_t>(cv),
                            P<int>(qp), P<int8_t>(run), P<int>(cand), bd, analyze, recon, P<int>(err), sdh,
-                           P<uint8_t>(ctb_mask), S(stream), ctu64, rdoq, rdoq_lam, slices);
+                           P<uint8_t>(ctb_mask), S(stream), ctu64, rdoq, rdoq_lam, slices, P<unsigned long long>(tsmap),
+                           P<int>(ts_lamq), P<int>(ts_count));
   }, py::arg("B"), py::arg("W"), py::arg("H"), py::arg("sy"), py::arg("su"), py::arg("sv"), py::arg("ry"), py::arg("ru"),
      py::arg("rv"), py::arg("ctu"), py::arg("cu"), py::arg("cy"), py::arg("cu_"), py::arg("cv"), py::arg("qp"),
      py::arg("run"), py::arg("cand"), py::arg("bd"), py::arg("analyze"), py::arg("recon"), py::arg("err"),
      py::arg("stream"), py::arg("sdh") = 0, py::arg("ctb_mask") = 0, py::arg("ctu64") = 0, py::arg("rdoq") = 0,
-     py::arg("rdoq_lam") = 0, py::arg("slices") = 1);
+     py::arg("rdoq_lam") = 0, py::arg("slices") = 1, py::arg("tsmap") = 0, py::arg("ts_lamq") = 0,
+     py::arg("ts_count") = 0);
   m.def("hevc_inter", [](int B, int W, int H, uintptr_t sy, uintptr_t su, uintptr_t sv, uintptr_t fy, uintptr_t fu,
                          uintptr_t fv, uintptr_t ry, uintptr_t ru, uintptr_t rv, uintptr_t ctu, uintptr_t cu, uintptr_t cy,
                          uintptr_t cu_, uintptr_t cv, uintptr_t qp, uintptr_t run, uintptr_t cand, uintptr_t mv,
                          uintptr_t me_cost, int bd, uintptr_t stream, int tu_split, int sdh, int intra_bias,
                          uintptr_t mvb, uintptr_t dirb, uintptr_t f1y, uintptr_t f1u, uintptr_t f1v, uintptr_t wp,
                          std::vector<uintptr_t> xref, uintptr_t mv8, int rdoq, int rdoq_lam, uintptr_t wpb, int rd_cbf,
-                         uintptr_t rd_lamq) {
+                         uintptr_t rd_lamq, uintptr_t tsmap, uintptr_t ts_lamq, uintptr_t ts_count) {
+    if ((tsmap != 0) != (ts_lamq != 0) || (tsmap != 0) != (ts_count != 0))
+      throw std::invalid_argument("hevc_inter: tsmap, ts_lamq and ts_count come together");
     // rd_cbf: every TU's levels checked against none (hevc_rdcbf.h); rd_lamq: int32 [52], lambda per QpY
     if ((rd_cbf != 0) != (rd_lamq != 0)) throw std::invalid_argument("hevc_inter: rd_cbf and its rd_lamq table come together");
     // wpb: x265 --weightb, int16 [B][2][6] list-0 / list-1 weights of a B picture
@@ -647,14 +661,16 @@ PYBIND11_MODULE(_hip, m) {
                            P<int16_t>(cy), P<int16_t>(cu_), P<int16_t>(cv), P<int>(qp), P<int8_t>(run), P<int>(cand),
                            P<int16_t>(mv), P<int>(me_cost), bd, tu_split, sdh, intra_bias, S(stream), P<int16_t>(mvb),
                            P<uint8_t>(dirb), P<uint16_t>(f1y), P<uint16_t>(f1u), P<uint16_t>(f1v), P<int16_t>(wp), xr,
-                           P<int16_t>(mv8), rdoq, rdoq_lam, P<int16_t>(wpb), P<int>(rd_lamq));
+                           P<int16_t>(mv8), rdoq, rdoq_lam, P<int16_t>(wpb), P<int>(rd_lamq),
+                           P<unsigned long long>(tsmap), P<int>(ts_lamq), P<int>(ts_count));
   }, py::arg("B"), py::arg("W"), py::arg("H"), py::arg("sy"), py::arg("su"), py::arg("sv"), py::arg("fy"), py::arg("fu"),
      py::arg("fv"), py::arg("ry"), py::arg("ru"), py::arg("rv"), py::arg("ctu"), py::arg("cu"), py::arg("cy"),
      py::arg("cu_"), py::arg("cv"), py::arg("qp"), py::arg("run"), py::arg("cand"), py::arg("mv"), py::arg("me_cost"),
      py::arg("bd"), py::arg("stream"), py::arg("tu_split") = 0, py::arg("sdh") = 0, py::arg("intra_bias") = 0,
      py::arg("mvb") = 0, py::arg("dirb") = 0, py::arg("f1y") = 0, py::arg("f1u") = 0, py::arg("f1v") = 0,
      py::arg("wp") = 0, py::arg("xref") = std::vector<uintptr_t>{}, py::arg("mv8") = 0, py::arg("rdoq") = 0,
-     py::arg("rdoq_lam") = 0, py::arg("wpb") = 0, py::arg("rd_cbf") = 0, py::arg("rd_lamq") = 0);
+     py::arg("rdoq_lam") = 0, py::arg("wpb") = 0, py::arg("rd_cbf") = 0, py::arg("rd_lamq") = 0,
+     py::arg("tsmap") = 0, py::arg("ts_lamq") = 0, py::arg("ts_count") = 0);
   // mc_block (hevc_mc.h) on ncase blocks of planted reference planes [ph, pw] (uint16): cases
   // int16 [ncase, 6] = block x, y, list-0 vector, list-1 vector; out uint16 [ncase, n * n]
   m.def("hevc_mc_probe", [](int ncase, uintptr_t ref0, uintptr_t ref1, int pw, int ph, uintptr_t cases, uintptr_t out, int nt,
@@ -695,6 +711,20 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("nblk"), py::arg("src"), py::arg("pred"), py::arg("lev"), py::arg("rec"), py::arg("flag"), py::arg("terms"),
      py::arg("log2n"), py::arg("bd"), py::arg("qp"), py::arg("sdh"), py::arg("rdoq"), py::arg("rdoq_lam"), py::arg("lamq"),
      py::arg("stream"));
+  // hv::tskip_tu after hv::transform_quant_block on nblk 4x4 source / prediction blocks [nblk, 4, 4]
+  // (uint16): the winner's levels (int16), reconstructed samples (uint16), transform_skip_flag and
+  // cbf (int32 [nblk, 2]) and D_A, D_B, R_A, R_B (int64 [nblk, 4]) per block
+  m.def("hevc_tskip_probe", [](int nblk, uintptr_t src, uintptr_t pred, uintptr_t lev, uintptr_t rec, uintptr_t flag,
+                               uintptr_t terms, int bd, int qp, int intra, int dst, int scan, int sdh, int rdoq,
+                               int rdoq_lam, int lamq, uintptr_t stream) {
+    if (!src || !pred || !lev || !rec || !flag || !terms) throw std::invalid_argument("hevc_tskip_probe: null buffer");
+    if (mivc_launch_hevc_tskip_probe(nblk, P<uint16_t>(src), P<uint16_t>(pred), P<int16_t>(lev), P<uint16_t>(rec), P<int>(flag),
+                                     P<long long>(terms), bd, qp, intra, dst, scan, sdh, rdoq, rdoq_lam, lamq, S(stream)) != 0)
+      throw std::invalid_argument("hevc_tskip_probe: bd 8 / 10, qp 0..51 + 6 (bd - 8), dst with intra only, scan 0..2, "
+                                  "rdoq 0..2, rdoq_lam 0..1472, lamq 0..2^23");
+  }, py::arg("nblk"), py::arg("src"), py::arg("pred"), py::arg("lev"), py::arg("rec"), py::arg("flag"), py::arg("terms"),
+     py::arg("bd"), py::arg("qp"), py::arg("intra"), py::arg("dst"), py::arg("scan"), py::arg("sdh"), py::arg("rdoq"),
+     py::arg("rdoq_lam"), py::arg("lamq"), py::arg("stream"));
   m.def("hevc_b", [](int mode, int B, int wmb, int hmb, uintptr_t src, uintptr_t ref0, uintptr_t ref1, uintptr_t hp0,
                      uintptr_t hp1, uintptr_t mv0, uintptr_t mv1, uintptr_t cost0, uintptr_t cost1, uintptr_t pm0,
                      uintptr_t pm1, uintptr_t tmv, uintptr_t tdir, uintptr_t mvb_in, uintptr_t dir_in, uintptr_t mvb_out,
@@ -802,15 +832,25 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("mv_out"), py::arg("cost"), py::arg("pm"), py::arg("qp"), py::arg("aq"), py::arg("stream"),
      py::arg("ctu64") = 0, py::arg("slices") = 1);
   m.def("hevc_entropy_state_bytes", [](int W, int H) { return mivc_hevc_entropy_state_bytes(W, H); });
+  // bytes of one substream's saved CABAC contexts: `gctx` of hevc_entropy holds B * substreams of them
+  m.def("hevc_entropy_ctx_bytes", [] { return mivc_hevc_entropy_ctx_bytes(); });
   // GPU CABAC slice data of B pictures of one coding step (kernels/hevc_entropy.hip); `pic` is
   // the step's hevc::CoderPic (host module hevc_coder_pic), substreams packed into pinned `dst`
   m.def("hevc_entropy", [](py::bytes pic, int B, uintptr_t qp, uintptr_t ctu, uintptr_t cu, uintptr_t col,
                            uintptr_t nzmap, uintptr_t cy, uintptr_t cb, uintptr_t cr, uintptr_t state,
                            long long state_bytes, uintptr_t out, unsigned cap, uintptr_t sizes, uintptr_t errs,
                            uintptr_t offs, uintptr_t offs_host, uintptr_t dst, unsigned long long dst_cap,
-                           uintptr_t overflow, uintptr_t stream, uintptr_t prof, uintptr_t gprog, uintptr_t gctx) {
+                           uintptr_t overflow, uintptr_t stream, uintptr_t prof, uintptr_t gprog, uintptr_t gctx,
+                           long long gctx_bytes, uintptr_t tsmap) {
     const std::string ps = pic;
     if (ps.size() != sizeof(mivc::hevc::CoderPic)) throw std::invalid_argument("hevc_entropy: pic is not a CoderPic");
+    if (gctx) {  // [B][substreams] saved contexts
+      mivc::hevc::CoderPic cp;
+      std::memcpy(&cp, ps.data(), sizeof(cp));
+      const long long nsub = cp.wpp ? cp.hctu : cp.slices;
+      if (B < 0 || nsub < 1 || gctx_bytes < B * nsub * mivc_hevc_entropy_ctx_bytes())
+        throw std::invalid_argument("hevc_entropy: gctx needs B * substreams * hevc_entropy_ctx_bytes() bytes");
+    }
     if (!ctu || !cu || !nzmap || !cy || !cb || !cr || !state || !out || !sizes || !errs || !offs || !offs_host || !dst)
       throw std::invalid_argument("hevc_entropy: null buffer");
     if (mivc_launch_hevc_entropy(ps.data(), B, P<int>(qp), P<void>(ctu), P<void>(cu), P<void>(col),
@@ -818,12 +858,14 @@ PYBIND11_MODULE(_hip, m) {
                                  P<uint8_t>(state), state_bytes, P<uint8_t>(out), cap, P<unsigned>(sizes), P<int>(errs),
                                  P<unsigned long long>(offs), P<unsigned long long>(offs_host), P<uint8_t>(dst), dst_cap,
                                  P<int>(overflow), S(stream), P<unsigned long long>(prof), P<int>(gprog),
-                                 P<void>(gctx)) != 0)
-      throw std::invalid_argument("hevc_entropy: unsupported geometry (substreams <= 100, cap % 16, state size)");
+                                 P<void>(gctx), P<unsigned long long>(tsmap)) != 0)
+      throw std::invalid_argument("hevc_entropy: unsupported geometry (substreams <= 100, cap % 16, state size), or a "
+                                  "transform skip map without CoderPic::tskip");
   }, py::arg("pic"), py::arg("B"), py::arg("qp"), py::arg("ctu"), py::arg("cu"), py::arg("col"), py::arg("nzmap"),
      py::arg("cy"), py::arg("cb"), py::arg("cr"), py::arg("state"), py::arg("state_bytes"), py::arg("out"), py::arg("cap"),
      py::arg("sizes"), py::arg("errs"), py::arg("offs"), py::arg("offs_host"), py::arg("dst"), py::arg("dst_cap"),
-     py::arg("overflow"), py::arg("stream"), py::arg("prof") = 0, py::arg("gprog") = 0, py::arg("gctx") = 0);
+     py::arg("overflow"), py::arg("stream"), py::arg("prof") = 0, py::arg("gprog") = 0, py::arg("gctx") = 0,
+     py::arg("gctx_bytes") = 0, py::arg("tsmap") = 0);
   m.def("hevc_qp_fixup", [](int B, int W, int H, uintptr_t ctu, uintptr_t cu, uintptr_t qp, uintptr_t run, int wpp,
                             uintptr_t stream, int ctu64, int slices) {
     if (slices < 1 || slices > 16 || slices > (H / 32 + (ctu64 ? 1 : 0)) >> (ctu64 ? 1 : 0))

@@ -251,13 +251,16 @@ __device__ __forceinline__ bool transform_quant_mfma(const DctLds& D, int* R, in
 
 // RDOQ: the instance that can run rate-distortion optimised quantisation (p.rdoq > 0 takes the
 // packed-word path as sign data hiding does, and bypasses the matrix-core form); the default
-// instance holds none of its code
-template <bool RDOQ = false>
+// instance holds none of its code.  TS: the transform skip form of a 4x4 TU (hevc_tskip.h): the
+// residual shifted to the coefficients' scale (15 - bd - log2n) enters the same quantiser, and the
+// dequantised levels are rescaled per 8.6.4.2 (tsShift 7) instead of inverse-transformed; only
+// the transform skip instances of the kernels hold it
+template <bool RDOQ = false, bool TS = false>
 __device__ __forceinline__ bool transform_quant_block(const DctLds& D, int* R, int* S, int16_t* lev, int lstride,
                                                       const TqParams& p) {
   const int n = 1 << p.log2n, lg = p.log2n;
   const bool rdoq = RDOQ && p.rdoq > 0;
-  if (p.mfma && !p.dst && p.sdh_scan < 0 && !rdoq && (lg == 4 || lg == 5)) {
+  if (!TS && p.mfma && !p.dst && p.sdh_scan < 0 && !rdoq && (lg == 4 || lg == 5)) {
     wave_sync();  // R was written by other lanes
     return lg == 5 ? transform_quant_mfma<5>(D, R, lev, lstride, p) : transform_quant_mfma<4>(D, R, lev, lstride, p);
   }
@@ -265,9 +268,11 @@ __device__ __forceinline__ bool transform_quant_block(const DctLds& D, int* R, i
   auto cn = [&](const DctLds& M, int l2, int k, int m) { return dst ? static_cast<int>(M.dst[k][m]) : hv::cn(M, l2, k, m); };
   // forward, stage 1 (rows): S[y][k] = (sum_x R[y][x] * C[k][x] + rnd) >> sh1
   const int sh1 = lg + p.bd - 9, r1 = 1 << (sh1 - 1);
-  wave_matmul(n, [&](int y, int x) { return R[y * 32 + x]; }, [&](int x, int k) { return cn(D, lg, k, x); },
-              [&](int y, int k, int v) { S[y * 32 + k] = (v + r1) >> sh1; });
-  wave_sync();
+  if constexpr (!TS) {
+    wave_matmul(n, [&](int y, int x) { return R[y * 32 + x]; }, [&](int x, int k) { return cn(D, lg, k, x); },
+                [&](int y, int k, int v) { S[y * 32 + k] = (v + r1) >> sh1; });
+    wave_sync();
+  }
   // stage 2 (columns): coefficient (v, u) = (sum_y C[v][y] * S[y][u] + rnd) >> sh2
   const int sh2 = lg + 6, r2 = 1 << (sh2 - 1);
   const int qm = p.qp % 6, qs = p.qp / 6;
@@ -278,34 +283,41 @@ __device__ __forceinline__ bool transform_quant_block(const DctLds& D, int* R, i
   const int dsh = p.bd + lg - 5;
   const int64_t drnd = 1ll << (dsh - 1);
   int any = 0;
-  wave_matmul(n, [&](int v, int y) { return cn(D, lg, v, y); }, [&](int y, int u) { return S[y * 32 + u]; },
-              [&](int v, int u, int c) {
-                c = (c + r2) >> sh2;
-                const int a = c < 0 ? -c : c;
-                int l = static_cast<int>((static_cast<int64_t>(a) * qscale + qoff) >> qbits);
-                l = l > 32767 ? 32767 : l;
-                if (rdoq) {  // the coefficient itself: rdoq_block chooses the level below
-                  R[v * 32 + u] = c;
-                  return;
-                }
-                if (p.sdh_scan >= 0) {
-                  // level, quantisation remainder (HM deltaU) and coefficient sign, packed for
-                  // the parity pass below; dequantisation follows it
-                  const int dl = static_cast<int>(((static_cast<int64_t>(a) * qscale) - (static_cast<int64_t>(l) << qbits)) >>
-                                                  (qbits - 8));
-                  const int sl = c < 0 ? -l : l;
-                  R[v * 32 + u] = static_cast<int>((static_cast<uint32_t>(sl) & 0xFFFFu) |
-                                                   ((static_cast<uint32_t>(dl) & 0x7FFFu) << 16) | (c < 0 ? 0x80000000u : 0u));
-                  return;
-                }
-                l = c < 0 ? -l : l;
-                lev[v * lstride + u] = static_cast<int16_t>(l);
-                any |= l != 0;
-                // dequantise (8.6.3, flat scaling) into R for the inverse transform
-                int64_t d = ((static_cast<int64_t>(l) * dscale) << qs) + drnd;
-                d >>= dsh;
-                R[v * 32 + u] = static_cast<int>(d < -32768 ? -32768 : (d > 32767 ? 32767 : d));
-              });
+  // one coefficient (v, u) through the quantiser
+  auto quant = [&](int v, int u, int c) {
+    const int a = c < 0 ? -c : c;
+    int l = static_cast<int>((static_cast<int64_t>(a) * qscale + qoff) >> qbits);
+    l = l > 32767 ? 32767 : l;
+    if (rdoq) {  // the coefficient itself: rdoq_block chooses the level below
+      R[v * 32 + u] = c;
+      return;
+    }
+    if (p.sdh_scan >= 0) {
+      // level, quantisation remainder (HM deltaU) and coefficient sign, packed for
+      // the parity pass below; dequantisation follows it
+      const int dl = static_cast<int>(((static_cast<int64_t>(a) * qscale) - (static_cast<int64_t>(l) << qbits)) >>
+                                      (qbits - 8));
+      const int sl = c < 0 ? -l : l;
+      R[v * 32 + u] = static_cast<int>((static_cast<uint32_t>(sl) & 0xFFFFu) |
+                                       ((static_cast<uint32_t>(dl) & 0x7FFFu) << 16) | (c < 0 ? 0x80000000u : 0u));
+      return;
+    }
+    l = c < 0 ? -l : l;
+    lev[v * lstride + u] = static_cast<int16_t>(l);
+    any |= l != 0;
+    // dequantise (8.6.3, flat scaling) into R for the inverse transform
+    int64_t d = ((static_cast<int64_t>(l) * dscale) << qs) + drnd;
+    d >>= dsh;
+    R[v * 32 + u] = static_cast<int>(d < -32768 ? -32768 : (d > 32767 ? 32767 : d));
+  };
+  if constexpr (TS) {
+    wave_sync();  // R was written by other lanes
+    const int i = lane_id();
+    if (i < 16) quant(i >> 2, i & 3, R[(i >> 2) * 32 + (i & 3)] << (13 - p.bd));
+  } else {
+    wave_matmul(n, [&](int v, int y) { return cn(D, lg, v, y); }, [&](int y, int u) { return S[y * 32 + u]; },
+                [&](int v, int u, int c) { quant(v, u, (c + r2) >> sh2); });
+  }
   wave_sync();
   if constexpr (RDOQ) {
     if (rdoq) rdoq_block(R, S, lg, p.scan, p.rdoq, p.rdoq_lam, qscale, qbits);
@@ -392,6 +404,12 @@ __device__ __forceinline__ bool transform_quant_block(const DctLds& D, int* R, i
   }
   const bool nz = __ballot(any) != 0;
   if (!nz) return false;  // residual is zero: R is all zero too
+  if constexpr (TS) {  // 8.6.4.2 with transform_skip_flag: r = (d << 7 + rnd) >> (20 - bd)
+    const int i = lane, sh = 20 - p.bd;
+    if (i < 16) R[(i >> 2) * 32 + (i & 3)] = ((R[(i >> 2) * 32 + (i & 3)] << 7) + (1 << (sh - 1))) >> sh;
+    wave_sync();
+    return true;
+  }
   // inverse, stage 1 (columns): S[y][x] = clip16((sum_k C[k][y] * R[k][x] + 64) >> 7)
   wave_matmul(n, [&](int y, int k) { return cn(D, lg, k, y); }, [&](int k, int x) { return R[k * 32 + x]; },
               [&](int y, int x, int v) {

@@ -66,6 +66,7 @@ struct HevcEntropyArgs {
   const CuInfo* cu;            // [B][nctb * 16]
   const CuInfo* col;           // [B][nctb * 16] collocated records, or null
   const unsigned long long* nzmap;  // [B][nctb][2]
+  const unsigned long long* tsmap;  // [B][nctb][2] transform skip bits (CoderLevels::tsmap), or null
   const int16_t* coef[3];      // level planes [B][H][W], [B][H / 2][W / 2]
   uint8_t* state;              // [B][state_bytes] picture state (hevc_entropy_state_bytes)
   long long state_bytes;
@@ -140,6 +141,7 @@ __global__ __launch_bounds__(1024) void hevc_entropy(HevcEntropyArgs a) {
   __syncthreads();
   CoderLevels lv;
   lv.nzmap = reinterpret_cast<const uint64_t*>(a.nzmap) + static_cast<size_t>(b) * nctb * 2;
+  if (a.tsmap) lv.tsmap = reinterpret_cast<const uint64_t*>(a.tsmap) + static_cast<size_t>(b) * nctb * 2;
   lv.plane[0] = a.coef[0] + static_cast<size_t>(b) * W * H;
   lv.plane[1] = a.coef[1] + static_cast<size_t>(b) * (W / 2) * (H / 2);
   lv.plane[2] = a.coef[2] + static_cast<size_t>(b) * (W / 2) * (H / 2);
@@ -390,17 +392,21 @@ __global__ __launch_bounds__(256) void hevc_entropy_gather(const uint8_t* __rest
 using namespace mivc::gpu;
 
 extern "C" long long mivc_hevc_entropy_state_bytes(int W, int H) { return entropy_state_bytes(W, H); }
+// bytes of one substream's saved contexts in gctx ([B][nsub] of them)
+extern "C" long long mivc_hevc_entropy_ctx_bytes() { return static_cast<long long>(mivc::hevc::kNumCtx * sizeof(CtxState)); }
 
 // B pictures of one coding step.  pic: the step's CoderPic (hevc_coder_pic); sizes / errs:
 // [B, nsub]; offs: [B * nsub + 1] device, offs_host the same in pinned host memory; dst:
-// pinned host memory of dst_cap bytes.  Returns -1 on bad geometry.
+// pinned host memory of dst_cap bytes; tsmap: the transform skip map (needs CoderPic::tskip), or
+// null.  Returns -1 on bad geometry.
 extern "C" int mivc_launch_hevc_entropy(const void* pic, int B, const int* qp, const void* ctu, const void* cu,
                                         const void* col, const unsigned long long* nzmap, const int16_t* cy,
                                         const int16_t* cb, const int16_t* cr, uint8_t* state, long long state_bytes,
                                         uint8_t* out, unsigned cap, unsigned* sizes, int* errs,
                                         unsigned long long* offs, unsigned long long* offs_host, uint8_t* dst,
                                         unsigned long long dst_cap, int* overflow, void* stream,
-                                        unsigned long long* prof, int* gprog, void* gctx) {
+                                        unsigned long long* prof, int* gprog, void* gctx,
+                                        const unsigned long long* tsmap) {
   HevcEntropyArgs a{};
   a.prof = prof;
   a.pic = *static_cast<const CoderPic*>(pic);
@@ -414,7 +420,9 @@ extern "C" int mivc_launch_hevc_entropy(const void* pic, int B, const int* qp, c
   a.ctu = static_cast<const CtuInfo*>(ctu);
   a.cu = static_cast<const CuInfo*>(cu);
   a.col = static_cast<const CuInfo*>(col);
+  if (tsmap && !a.pic.tskip) return -1;
   a.nzmap = nzmap;
+  a.tsmap = tsmap;
   a.coef[0] = cy;
   a.coef[1] = cb;
   a.coef[2] = cr;
@@ -455,7 +463,7 @@ extern "C" int mivc_launch_hevc_entropy(const void* pic, int B, const int* qp, c
   a.K = K;
   a.gprog = gprog;
   a.gctx = static_cast<CtxState*>(gctx);
-  // working contexts per wave, plus (K == 1) each row's contexts after CTU 1: <= 35 KB
+  // working contexts per wave, plus (K == 1) each row's contexts after CTU 1: <= 36 KB
   const size_t lds = static_cast<size_t>(K > 1 ? nw : nw + nsub) * mivc::hevc::kNumCtx * sizeof(CtxState);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (K > 1) {

@@ -151,9 +151,13 @@ extern "C" void mivc_launch_hevc_inter(int B, int W, int H, const uint16_t* sy, 
                                        int intra_bias, void* stream, const int16_t* mvb, const uint8_t* dirb,
                                        const uint16_t* f1y, const uint16_t* f1u, const uint16_t* f1v,
                                        const int16_t* wp, const uint16_t* const* xref, const int16_t* mv8, int rdoq,
-                                       int rdoq_lam, const int16_t* wpb, const int* rd_lamq) {
+                                       int rdoq_lam, const int16_t* wpb, const int* rd_lamq,
+                                       unsigned long long* tsmap, const int* ts_lamq, int* ts_count) {
   HevcInterArgs a;
   a.rd_lamq = rd_lamq;
+  a.tsmap = tsmap;  // all three or none (the binding checks)
+  a.ts_lamq = ts_lamq;
+  a.ts_count = ts_count;
   a.wp = wp;
   a.wpb = wpb;
   a.mv8 = mv8;
@@ -196,6 +200,11 @@ extern "C" void mivc_launch_hevc_inter(int B, int W, int H, const uint16_t* sy, 
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(hevc_p_decide, dim3(a.g.nctb(), B), dim3(64), 0, s, a);
   const dim3 grid(a.g.nctb() * 4, B);
+  if (tsmap) {  // transform skip on the chroma 4x4 TUs of 8x8 CUs: the TSK instances
+    if (rd_lamq) launch_hevc_inter_cu_tsk_rdc(a, grid, s, tu_split != 0, rdoq != 0, wpb != nullptr);
+    else launch_hevc_inter_cu_tsk(a, grid, s, tu_split != 0, rdoq != 0, wpb != nullptr);
+    return;
+  }
   if (rd_lamq) {  // every TU checked against no levels: the RDC instances
     launch_hevc_inter_cu_rdc(a, grid, s, tu_split != 0, rdoq != 0, wpb != nullptr);
     return;

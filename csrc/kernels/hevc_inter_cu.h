@@ -8,6 +8,7 @@
 #include "hevc_common.h"
 #include "hevc_mc.h"
 #include "hevc_rdcbf.h"
+#include "hevc_tskip.h"
 
 namespace mivc {
 namespace gpu {
@@ -52,6 +53,11 @@ struct HevcInterArgs {
   const int16_t* mv8;
   int rdoq, rdoq_lam;    // x265 --rdoq-level and its lambda (hevc_rdoq.h); the RDOQ instances read them
   const int* rd_lamq;    // [52] SSD lambda per QpY in 1 / 16 units (hevc_rdcbf.h); the RDC instances read it
+  // x265 --tskip (hevc_tskip.h; the TSK instances read them): the map [B, nctb, 2], the lambda
+  // table [52] and the counters of TUs coded with the flag set (this kernel adds to entry 2)
+  unsigned long long* tsmap;
+  const int* ts_lamq;
+  int* ts_count;
 };
 
 // plane c of RefPicList0[r] (constant indices only: no scratch)
@@ -94,9 +100,10 @@ __device__ __forceinline__ long long recon_ssd(const SH& S, const int* R, const 
 // every TU's levels against no levels by SSD + lambda * bits (hevc_rdcbf.h)
 // (the RDC instances without the quadtree ask for two waves per SIMD, not three: the check's live
 // values on top of the 168 registers of three would go to scratch; the LDS allows 2.5.  The
-// quadtree instances run one wave per SIMD either way)
-template <bool TSPLIT, bool RDOQ, bool WB, bool RDC>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RDC && !TSPLIT ? 2 : 3, 8))) void hevc_inter_cu(HevcInterArgs a) {
+// quadtree instances run one wave per SIMD either way); TSK: the instances with the transform
+// skip decision on the chroma 4x4 TUs of 8x8 CUs (hevc_tskip.h; registers as the RDC instances)
+template <bool TSPLIT, bool RDOQ, bool WB, bool RDC, bool TSK = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((RDC || TSK) && !TSPLIT ? 2 : 3, 8))) void hevc_inter_cu(HevcInterArgs a) {
   __shared__ typename std::conditional<TSPLIT, InterShared, InterSharedLean>::type S;
   __shared__ hv::DctLds D;
   const HevcGeom& g = a.g;
@@ -120,6 +127,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RDC && !TSPL
   const int qpl = qpy + off, qpc = hevc::chroma_qp_map(clampi(qpy, -off, 57)) + off;
   int lamq = 0;
   if constexpr (RDC) lamq = a.rd_lamq[clampi(qpy, 0, 51)];
+  int ts_lamq = 0;
+  if constexpr (TSK) ts_lamq = a.ts_lamq[clampi(qpy, 0, 51)];
   // a quadrant split into 8x8 inter CUs (x265's minimum CU) codes them one after another
   const int ncu = lg == 3 ? 4 : 1;
   for (int j = 0; j < ncu; ++j) {
@@ -261,7 +270,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RDC && !TSPL
     }
     if (!coded) {
       bool nz = hv::transform_quant_block<RDOQ>(D, S.R, S.S, lev, pw, tq(l2));
+      bool ts = false;
+      if constexpr (TSK) {  // the chroma 4x4 TU of an 8x8 CU: transform skip against the transform
+        if (c > 0 && lg == 3)
+          nz = hv::tskip_tu<RDOQ>(D, nz, S.pred, bs, S.R, S.S, src + static_cast<size_t>(by) * pw + bx, pw, lev, pw, tq(l2), 0,
+                                  maxv, ts_lamq, ts);
+      }
       if constexpr (RDC) nz = rdc(nz, 0, 0, l2, S.R, lev, pw, d0);
+      if constexpr (TSK) {
+        if (c > 0 && lg == 3 && lane == 0) {  // (a TU the check cleared codes no flag)
+          hv::tsmap_put(a.tsmap, cb, c, (bx & 15) >> 2, (by & 15) >> 2, ts && nz);
+          if (ts && nz) atomicAdd(a.ts_count + 2, 1);
+        }
+      }
       for (int k = 0; k < 4; ++k) cbfq[k] |= nz << c;
     }
     // (a block without levels has an all-zero dequantised residual in R)
@@ -284,6 +305,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RDC && !TSPL
 
 // the RDC instances (hevc_inter_rdcbf.hip); a.rd_lamq is set
 void launch_hevc_inter_cu_rdc(const HevcInterArgs& a, dim3 grid, hipStream_t s, bool tu_split, bool rdoq, bool wb);
+// the TSK instances without / with the check (hevc_inter_tskip.hip, hevc_inter_tskip_rdc.hip);
+// a.tsmap, a.ts_lamq and a.ts_count are set
+void launch_hevc_inter_cu_tsk(const HevcInterArgs& a, dim3 grid, hipStream_t s, bool tu_split, bool rdoq, bool wb);
+void launch_hevc_inter_cu_tsk_rdc(const HevcInterArgs& a, dim3 grid, hipStream_t s, bool tu_split, bool rdoq, bool wb);
 
 }  // namespace gpu
 }  // namespace mivc

@@ -14,6 +14,7 @@
 //   (wave-level matrix products in LDS, hevc_common.h).  In P pictures only intra
 //   CUs are visited (inter CUs were reconstructed by hevc_inter).
 #include "hevc_common.h"
+#include "hevc_tskip.h"
 
 namespace mivc {
 namespace gpu {
@@ -41,6 +42,12 @@ struct HevcIntraArgs {
                                           // where intra may beat the motion search); null = every CTB
   int ctu64;                              // 64x64 CTUs: the 32x32 blocks are coded in z-order inside them
   int slices;                             // independent slices of whole CTU rows (hevc_tables.h slice_of_row)
+  // x265 --tskip (hevc_tskip.h; the transform skip instances of hevc_intra_recon read them): the
+  // map [B, nctb, 2] (cleared per picture by the caller), the lambda table [52] and the counters
+  // of TUs coded with the flag set (intra luma, intra chroma, inter chroma)
+  unsigned long long* tsmap;
+  const int* ts_lamq;
+  int* ts_count;
 };
 
 constexpr int kNoIntra = 1 << 26;  // candidate cost of a CTB the analysis skipped (inter decisive)
@@ -523,10 +530,10 @@ struct ReconShared {
 };
 
 // reconstruct one CU component: refs from the LDS tile, predict, transform/quantise, store
-template <bool LUMA, bool RDOQ>
+template <bool LUMA, bool RDOQ, bool TSK = false>
 __device__ __forceinline__ bool recon_block(const HevcIntraArgs& a, ReconShared& S, const hv::DctLds& D, int slot,
                                             int comp, int rx, int ry, int cx, int cy, int log2n, int mode, int zc, int qpp,
-                                            bool dst = false) {
+                                            bool dst = false, int lamq = 0) {
   const HevcGeom& g = a.g;
   const int lane = lane_id();
   const int n = 1 << log2n;
@@ -578,7 +585,18 @@ __device__ __forceinline__ bool recon_block(const HevcIntraArgs& a, ReconShared&
     tp.rdoq = a.rdoq;
     tp.rdoq_lam = a.rdoq_lam;
   }
-  const bool nz = hv::transform_quant_block<RDOQ>(D, S.R, S.S, lev, pw, tp);
+  bool nz = hv::transform_quant_block<RDOQ>(D, S.R, S.S, lev, pw, tp);
+  if constexpr (TSK) {
+    if (log2n == 2) {  // transform skip against the transform (hevc_tskip.h)
+      bool ts;
+      nz = hv::tskip_tu<RDOQ>(D, nz, S.pred, 4, S.R, S.S, src + static_cast<size_t>(Y0) * pw + X0, pw, lev, pw, tp,
+                              hv::tu_scan_idx(true, LUMA, 2, mode), maxv, lamq, ts);
+      if (lane == 0) {
+        hv::tsmap_put(a.tsmap, static_cast<size_t>(slot) * g.nctb() + ry * g.wctb + rx, comp, cx >> 2, cy >> 2, ts);
+        if (ts) atomicAdd(a.ts_count + (LUMA ? 0 : 1), 1);
+      }
+    }
+  }
   uint16_t* rec = (LUMA ? a.rec_y : (comp == 1 ? a.rec_u : a.rec_v)) + slot * (LUMA ? g.ysize() : g.csize());
   for (int i = lane; i < n * n; i += 64) {
     const int x = i & (n - 1), y = i >> log2n;
@@ -595,7 +613,7 @@ __device__ __forceinline__ bool recon_block(const HevcIntraArgs& a, ReconShared&
 // One colour component per workgroup (comp = blockIdx.y): the three planes of a picture are
 // independent intra wavefronts (no cross-component prediction in Main / Main 10), so a slot's
 // luma, Cb and Cr run side by side on three CUs instead of one after another in one wave.
-template <bool RDOQ>
+template <bool RDOQ, bool TSK>
 __device__ __forceinline__ void hevc_recon_ctb(const HevcIntraArgs& a, ReconShared& S, const hv::DctLds& D, int slot,
                                                int rx, int ry, int run, int comp) {
   const HevcGeom& g = a.g;
@@ -639,6 +657,8 @@ __device__ __forceinline__ void hevc_recon_ctb(const HevcIntraArgs& a, ReconShar
   const int off = 6 * (a.bd - 8);
   const int qpl = qpy + off;
   const int qpc = hevc::chroma_qp_map(clampi(qpy, -off, 57)) + off;
+  int lamq = 0;
+  if constexpr (TSK) lamq = a.ts_lamq[clampi(qpy, 0, 51)];
   // ---- CUs in z-order
   for (int k = 0; k < 16;) {
     const int q = k >> 2;
@@ -655,13 +675,13 @@ __device__ __forceinline__ void hevc_recon_ctb(const HevcIntraArgs& a, ReconShar
       const int cx = gx * 8, cy = gy * 8;
       bool nz = false;
       if (!luma) {
-        nz = recon_block<false, RDOQ>(a, S, D, slot, comp, rx, ry, cx / 2, cy / 2, log2n - 1, mode, 4 * k, qpc);
+        nz = recon_block<false, RDOQ, TSK>(a, S, D, slot, comp, rx, ry, cx / 2, cy / 2, log2n - 1, mode, 4 * k, qpc, false, lamq);
       } else if (log2n == 3 && (__builtin_amdgcn_readfirstlane(cu->flags) & 8)) {
         // PART_NxN: four 4x4 luma PUs in z-order, DST, each predicted from the previous ones
         const uint32_t pm = __builtin_amdgcn_readfirstlane(*reinterpret_cast<const uint32_t*>(cu->mv));
         for (int j = 0; j < 4; ++j)
-          nz |= recon_block<true, RDOQ>(a, S, D, slot, 0, rx, ry, cx + (j & 1) * 4, cy + (j >> 1) * 4, 2,
-                                  static_cast<int>((pm >> (8 * j)) & 255u), 4 * k + j, qpl, true);
+          nz |= recon_block<true, RDOQ, TSK>(a, S, D, slot, 0, rx, ry, cx + (j & 1) * 4, cy + (j >> 1) * 4, 2,
+                                  static_cast<int>((pm >> (8 * j)) & 255u), 4 * k + j, qpl, true, lamq);
       } else {
         nz = recon_block<true, RDOQ>(a, S, D, slot, 0, rx, ry, cx, cy, log2n, mode, 4 * k, qpl);
       }
@@ -695,8 +715,9 @@ __device__ __forceinline__ void hevc_recon_ctb(const HevcIntraArgs& a, ReconShar
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-// RDOQ: the instance with rate-distortion optimised quantisation (kept out of the default one)
-template <bool RDOQ>
+// RDOQ: the instance with rate-distortion optimised quantisation (kept out of the default one);
+// TSK: the instances with the transform skip decision on 4x4 TUs (hevc_tskip.h)
+template <bool RDOQ, bool TSK = false>
 __global__ __launch_bounds__(64 * kHevcIntraWaves) void hevc_intra_recon(HevcIntraArgs a) {
   __shared__ ReconShared SS[kHevcIntraWaves];
   __shared__ hv::DctLds D;
@@ -734,7 +755,7 @@ __global__ __launch_bounds__(64 * kHevcIntraWaves) void hevc_intra_recon(HevcInt
         for (int q = 0; q < nq; ++q) {
           const int bx = (x << c64) + (q & 1), by = (y << c64) + (q >> 1);
           if (bx >= g.wctb || by >= g.hctb) continue;
-          hevc_recon_ctb<RDOQ>(a, S, D, slot, bx, by, run, comp);
+          hevc_recon_ctb<RDOQ, TSK>(a, S, D, slot, bx, by, run, comp);
         }
         row_publish(prog, y, x + 1);
       }
@@ -763,7 +784,7 @@ __global__ __launch_bounds__(64 * kHevcIntraWaves) void hevc_intra_recon(HevcInt
           const int bx = (x << c64) + (q & 1), by = (y << c64) + (q >> 1);
           if (bx >= g.wctb || by >= g.hctb) continue;
           if (block_work(bx, by)) {
-            hevc_recon_ctb<RDOQ>(a, S, D, slot, bx, by, run, comp);
+            hevc_recon_ctb<RDOQ, TSK>(a, S, D, slot, bx, by, run, comp);
           } else {
             if (lane_id() == 0) S.saved_x = -2;
             wave_sync();
@@ -810,6 +831,9 @@ static HevcIntraArgs make_intra_args(int B, int W, int H, const uint16_t* sy, co
   a.ctb_mask = nullptr;
   a.ctu64 = 0;
   a.slices = 1;
+  a.tsmap = nullptr;
+  a.ts_lamq = nullptr;
+  a.ts_count = nullptr;
   return a;
 }
 
@@ -817,15 +841,22 @@ extern "C" void mivc_launch_hevc_intra(int B, int W, int H, const uint16_t* sy, 
                                        uint16_t* ry, uint16_t* ru, uint16_t* rv, void* ctu, void* cu, int16_t* cy,
                                        int16_t* cu_, int16_t* cv, const int* qp, const int8_t* run, int* cand, int bd,
                                        int analyze, int recon, int* err, int sdh, const uint8_t* ctb_mask,
-                                       void* stream, int ctu64, int rdoq, int rdoq_lam, int slices) {
+                                       void* stream, int ctu64, int rdoq, int rdoq_lam, int slices,
+                                       unsigned long long* tsmap, const int* ts_lamq, int* ts_count) {
   HevcIntraArgs a = make_intra_args(B, W, H, sy, su, sv, ry, ru, rv, ctu, cu, cy, cu_, cv, qp, run, cand, bd, err, sdh);
   a.ctb_mask = ctb_mask;
   a.ctu64 = ctu64;
   a.rdoq = rdoq;
   a.rdoq_lam = rdoq_lam;
   a.slices = slices;
+  a.tsmap = tsmap;  // all three or none (the binding checks)
+  a.ts_lamq = ts_lamq;
+  a.ts_count = ts_count;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (analyze) hipLaunchKernelGGL(hevc_intra_analyze, dim3(a.g.nctb(), B), dim3(256), 0, s, a);
-  if (recon && rdoq) hipLaunchKernelGGL(hevc_intra_recon<true>, dim3(B, 3, slices), dim3(64 * kHevcIntraWaves), 0, s, a);
+  if (recon && tsmap) {
+    if (rdoq) hipLaunchKernelGGL((hevc_intra_recon<true, true>), dim3(B, 3, slices), dim3(64 * kHevcIntraWaves), 0, s, a);
+    else hipLaunchKernelGGL((hevc_intra_recon<false, true>), dim3(B, 3, slices), dim3(64 * kHevcIntraWaves), 0, s, a);
+  } else if (recon && rdoq) hipLaunchKernelGGL(hevc_intra_recon<true>, dim3(B, 3, slices), dim3(64 * kHevcIntraWaves), 0, s, a);
   else if (recon) hipLaunchKernelGGL(hevc_intra_recon<false>, dim3(B, 3, slices), dim3(64 * kHevcIntraWaves), 0, s, a);
 }

@@ -251,6 +251,8 @@ HEVC_PARAMS = {
     "signhide": ("sdh", _flag),
     "no-signhide": ("sdh", lambda v: not _flag(v)),
     "rdoq-level": ("rdoq_level", _int_in(0, 2)),
+    "tskip": ("tskip", _flag),  # (tskip-fast stays unknown: the decision here is always the full comparison)
+    "no-tskip": ("tskip", lambda v: not _flag(v)),
     "tu-inter-depth": ("tu_inter_depth", lambda v: _int_in(1, 2)(v) - 1),
     "scenecut": ("scenecut", _int_in(0, 100)),
     "rc-lookahead": ("lookahead", lambda v: int(v) > 0),

@@ -216,6 +216,16 @@ class HevcParams:
     # (cost only).  1 <= slices <= min(16, CTU rows); measurements: profiles/hevc_slices.md --
     # opt-in, in no preset
     slices: int = 1
+    # x265 --tskip: transform skip for 4x4 TUs (csrc/kernels/hevc_tskip.h; the PPS's
+    # transform_skip_enabled_flag, a transform_skip_flag per 4x4 TU).  Intra luma 4x4 TUs (PART_NxN),
+    # the chroma 4x4 TUs of 8x8 intra CUs and of 8x8 inter CUs quantise the residual samples
+    # themselves as a second candidate (same quantiser, sign data hiding and RDOQ) and keep it when
+    # 256 * D_B + lamq * (R_B + 34) beats the transform's cost (exact SSDs, RDOQ's static bin
+    # costs, the rd_cbf lambda table times ``tskip_lambda``); rd_cbf then checks the winner.  The
+    # open-loop analysis and the mode decisions are untouched.  It pays on text, UI and line art
+    # (utils/screen_synth.py); measurements: profiles/hevc_tskip.md -- opt-in, in no preset
+    tskip: bool = False
+    tskip_lambda: float = 1.0
 
     def ctu_rows(self) -> int:
         """CTU rows of the coded picture (64-sample rows with ctu64, else 32-sample rows)."""
@@ -232,6 +242,8 @@ class HevcParams:
         tag = f"hevc {self.width}x{self.height} {rate} ctu{64 if self.ctu64 else 32}"
         if self.slices > 1:
             tag += f" slices{self.slices}"
+        if self.tskip:
+            tag += " tskip"
         return tag
 
     def eff_refs(self) -> int:
@@ -262,12 +274,21 @@ class HevcParams:
                     cu_qp_delta=int(self.adaptive_qp()), tu_inter_depth=int(self.tu_inter_depth), sdh=int(self.sdh),
                     level_idc=int(self.level_idc), bframes=self.eff_bframes(), tmvp=int(self.tmvp and not self.intra_only),
                     pyramid=int(self.pyramid), ctu64=int(self.ctu64), weightp=int(self.eff_weightp()),
-                    weightb=int(self.eff_weightb()), refs=self.eff_refs(), slices=int(self.slices))
+                    weightb=int(self.eff_weightb()), refs=self.eff_refs(), slices=int(self.slices),
+                    tskip=int(bool(self.tskip)))
 
     def frame_qps(self) -> tuple[int, int]:
         qp_p = int(round(self.crf)) if self.crf is not None else int(self.qp)
         qp_p = max(0, min(51, qp_p))
         return max(0, qp_p - self.ip_offset), qp_p
+
+
+class StatCounts(tuple):
+    """A tuple of counters in ``GpuHevcEncoder.stats`` (whose other entries are numbers, and whose
+    readers may round every entry): rounding leaves the counts as they are."""
+
+    def __round__(self, ndigits=None):
+        return self
 
 
 def rd_cbf_lamq_table(rd_cbf_lambda: float, bit_depth: int) -> list[int]:
@@ -338,6 +359,10 @@ class GpuHevcEncoder:
             raise ValueError("rdoq_lambda must be in (0, 4]")
         if not 0.0 < float(params.rd_cbf_lambda) <= 4.0:
             raise ValueError("rd_cbf_lambda must be in (0, 4]")
+        if not isinstance(params.tskip, (bool, int)) or params.tskip not in (0, 1, False, True):
+            raise ValueError("tskip must be a bool")
+        if not 0.0 < float(params.tskip_lambda) <= 4.0:
+            raise ValueError("tskip_lambda must be in (0, 4]")
         params.check_slices()
         self.p = params
         self.B = int(slots)
@@ -364,6 +389,12 @@ class GpuHevcEncoder:
         if params.rd_cbf and not params.intra_only:
             self.rd_lamq = torch.tensor(rd_cbf_lamq_table(params.rd_cbf_lambda, params.bit_depth), dtype=torch.int32, device=dev)
             self.rd_cbf_kw = dict(rd_cbf=1, rd_lamq=self.rd_lamq.data_ptr())
+        # tskip: the lambda table and the counters of the reconstruction launches; the maps are
+        # allocated beside the sub-block maps below
+        self.tsmaps = None
+        if params.tskip:
+            self.ts_lamq = torch.tensor(rd_cbf_lamq_table(params.tskip_lambda, params.bit_depth), dtype=torch.int32, device=dev)
+            self.ts_count = torch.zeros((3,), dtype=torch.int32, device=dev)
         self.nb = params.eff_bframes()
         self.nrefs = params.eff_refs()
         # reconstruction buffers: one per DPB slot of a reference picture (models/gop.py
@@ -434,6 +465,8 @@ class GpuHevcEncoder:
         # overlaps step t + 1)
         self.pack_cap = self.nctb * 96  # 4x4 blocks per slot: every block of every CTB
         self.nzmaps = [torch.zeros((B, self.nctb, 2), dtype=torch.int64, device=dev) for _ in range(2)]
+        if params.tskip:  # transform skip bits of the 4x4 TUs, laid out like the sub-block maps
+            self.tsmaps = [torch.zeros((B, self.nctb, 2), dtype=torch.int64, device=dev) for _ in range(2)]
         self.nzoffs = [torch.zeros((B, self.nctb), dtype=torch.int32, device=dev) for _ in range(2)]
         self.nzcnt = torch.zeros((B, self.nctb), dtype=torch.int32, device=dev)
         self.copy_stream = torch.cuda.Stream(device=dev)
@@ -535,7 +568,7 @@ class GpuHevcEncoder:
         # narrow batches spread a picture over several workgroups (kernels/hevc_entropy.hip):
         # row progress and the row contexts after CTU 1 then go through device memory
         self.ent_gprog = torch.zeros((n,), dtype=torch.int32, device=dev)
-        self.ent_gctx = torch.zeros((n * 151 * 2,), dtype=torch.uint8, device=dev)  # kNumCtx CtxStates per row
+        self.ent_gctx = torch.zeros((n * int(self.hip.hevc_entropy_ctx_bytes()),), dtype=torch.uint8, device=dev)
         # pinned output per host set: half a byte per luma sample of every picture of a step
         self.ent_dst_cap = max(1 << 22, B * W * H // 2)
         self.ent_host = None
@@ -577,7 +610,8 @@ class GpuHevcEncoder:
             def pin(t):
                 return torch.empty(t.shape, dtype=t.dtype).pin_memory()
             self.host_bufs = [[pin(self.ctus[0]), pin(self.cus[0]), pin(self.nzmaps[0]), pin(self.nzoffs[0]),
-                               torch.empty((self.B, self.pack_cap * 16), dtype=torch.int16).pin_memory()]
+                               torch.empty((self.B, self.pack_cap * 16), dtype=torch.int16).pin_memory()] +
+                              ([pin(self.tsmaps[0])] if self.tsmaps is not None else [])
                               for _ in range(3)]
         return self.host_bufs
 
@@ -991,6 +1025,8 @@ class GpuHevcEncoder:
         st = self.stage_timer
         gate_sum: list[torch.Tensor] = []
         tmvp = bool(cfg.get("tmvp", 0))
+        if self.tsmaps is not None:
+            self.ts_count.zero_()
         anchor_cu: dict = {}   # display index of a reference picture -> (host copy of its CU records or None, l0, l1)
         ref_lists: dict = {}   # display index of a reference picture -> its (l0, l1) display indices
         anchor_meta: dict = {}  # (GPU entropy) display index of a reference picture -> (DPB slot, l0, l1, refs0)
@@ -1045,6 +1081,10 @@ class GpuHevcEncoder:
             rdoq = dict(rdoq=int(self.p.rdoq_level), rdoq_lam=int(round(float(self.p.rdoq_lambda) * 368))) \
                 if self.p.rdoq_level else {}
             ns = int(self.p.slices)  # slices per picture (HevcParams.slices)
+            ts_kw = {}
+            if self.tsmaps is not None:  # the picture's transform skip map starts empty
+                self.tsmaps[kb].zero_()
+                ts_kw = dict(tsmap=p(self.tsmaps[kb]), ts_lamq=p(self.ts_lamq), ts_count=p(self.ts_count))
             intra_args = (B, self.W, self.H, p(self.src[0]), p(self.src[1]), p(self.src[2]), p(cur[0]), p(cur[1]),
                           p(cur[2]), p(self.ctu), p(self.cu), p(self.coef[0]), p(self.coef[1]), p(self.coef[2]),
                           p(self.ctb_qp), p(self.run), p(self.cand), bd)
@@ -1053,7 +1093,7 @@ class GpuHevcEncoder:
                 self.prev_mv.zero_()  # no motion predictors across a closed GOP (or from an earlier call)
                 with st("intra_i"):
                     self.hip.hevc_intra(*intra_args, 1, 1, p(self.err), s, int(self.p.sdh), 0, int(self.p.ctu64), slices=ns,
-                                        **rdoq)
+                                        **rdoq, **ts_kw)
             else:
                 self.run.fill_(2)
                 ref8, hp = self.ref8s[r0], self.me_hps[r0]
@@ -1185,10 +1225,11 @@ class GpuHevcEncoder:
                                         p(ref[1]), p(ref[2]), p(cur[0]), p(cur[1]), p(cur[2]), p(self.ctu), p(self.cu),
                                         p(self.coef[0]), p(self.coef[1]), p(self.coef[2]), p(self.ctb_qp), p(self.run),
                                         p(self.cand), p(self.mv), p(self.me_cost), bd, s, int(self.p.tu_inter_depth),
-                                        int(self.p.sdh), int(self.p.intra_bias_p), **inter_kw, **rdoq, **self.rd_cbf_kw)
+                                        int(self.p.sdh), int(self.p.intra_bias_p), **inter_kw, **rdoq, **self.rd_cbf_kw,
+                                        **ts_kw)
                 with st("intra_recon"):
                     self.hip.hevc_intra(*intra_args, 0, 1, p(self.err), s, int(self.p.sdh), 0,
-                                        int(self.p.ctu64), slices=ns, **rdoq)   # intra CUs, wavefront
+                                        int(self.p.ctu64), slices=ns, **rdoq, **ts_kw)   # intra CUs, wavefront
                 if pic.kind == "P":
                     self.prev_mv.copy_(self.mv)
             self.hip.hevc_qp_fixup(B, self.W, self.H, p(self.ctu), p(self.cu), p(self.qp), p(self.run), int(self.p.wpp), s,
@@ -1255,16 +1296,19 @@ class GpuHevcEncoder:
                     self.copy_stream.wait_event(ev)
                     for dst, src_t in zip(host[:4], (self.ctu, self.cu, nzmap, nzoff)):
                         dst.copy_(src_t, non_blocking=True)
+                    if self.tsmaps is not None:
+                        host[5].copy_(self.tsmaps[kb], non_blocking=True)
                     done = torch.cuda.Event()
                     done.record(self.copy_stream)
                     self.copy_done[kb].record(self.copy_stream)
                 ctu, cu = host[0].numpy(), host[1].numpy()
                 nz, off, lv = host[2].numpy().view(np.uint64), host[3].numpy().view(np.uint32), host[4].numpy()
+                tsm = host[5].numpy().view(np.uint64) if self.tsmaps is not None else None
                 t1 = time.perf_counter()
                 t_gpu += t1 - t0
 
                 def job(done=done, pic=pic, qcol=qcol, ctu=ctu, cu=cu, nz=nz, off=off, lv=lv, i0=idr_d, wrow=wrow,
-                        wrow1=wrow1):
+                        wrow1=wrow1, tsm=tsm):
                     done.synchronize()
                     tj = time.perf_counter()
                     # POC counts display pictures from the latest IDR
@@ -1294,9 +1338,11 @@ class GpuHevcEncoder:
                             fp["col_cu"] = None if col[0] is None else col[0][b]
                         fps.append(fp)
                     if self.cu_stats is None:
-                        r = self.host.hevc_write_slices_packed(cfg, fps, ctu, cu, nz, off, lv, self.entropy_threads)
+                        r = self.host.hevc_write_slices_packed(cfg, fps, ctu, cu, nz, off, lv, self.entropy_threads,
+                                                               tsmap=tsm)
                     else:  # diagnostics: CU mix per picture type (tools/diag/hevc_bframe_stats.py)
-                        rs = self.host.hevc_write_slices_packed(cfg, fps, ctu, cu, nz, off, lv, self.entropy_threads, True)
+                        rs = self.host.hevc_write_slices_packed(cfg, fps, ctu, cu, nz, off, lv, self.entropy_threads, True,
+                                                                tsmap=tsm)
                         r = [n for n, _ in rs]
                         agg = self.cu_stats.setdefault(pic.kind + ("ref" if pic.kind == "B" and pic.ref else ""), {})
                         for _, stt in rs:
@@ -1373,7 +1419,8 @@ class GpuHevcEncoder:
                                   p(self.coef[1]), p(self.coef[2]), p(self.ent_state), self.ent_state_bytes,
                                   p(self.ent_outs[hb]), self.ent_cap, p(self.ent_sizes), p(self.ent_errs), p(self.ent_offs),
                                   eh["offs"].data_ptr(), eh["dst"].data_ptr(), self.ent_dst_cap, p(self.ent_over), sc,
-                                  self._entropy_prof(pic.kind), p(self.ent_gprog), p(self.ent_gctx))
+                                  self._entropy_prof(pic.kind), p(self.ent_gprog), p(self.ent_gctx), self.ent_gctx.numel(),
+                                  p(self.tsmaps[kb]) if self.tsmaps is not None else 0)
             # the batch's QP table is freed when the encode returns: keep its block from being
             # reused (by the compute stream's next batch) before this stream has read it
             qp_row.record_stream(cs)
@@ -1423,6 +1470,8 @@ class GpuHevcEncoder:
         if int(self.err.item()) != 0:
             raise RuntimeError("HEVC encoder: wavefront progress timeout")
         t2 = time.perf_counter()
+        if self.tsmaps is not None:  # 4x4 TUs coded with transform_skip_flag 1: intra luma, intra chroma, inter chroma
+            self.stats["tskip_tus"] = StatCounts(int(v) for v in self.ts_count.tolist())
         bits = [[0] * F for _ in range(B)]
         for t, f in futs:
             for b, nal in enumerate(f.result()):

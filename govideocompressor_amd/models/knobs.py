@@ -81,6 +81,8 @@ HEVC = {
     "MIVC_HEVC_AQ_MODE": "aq_mode",
     "MIVC_HEVC_WEIGHTB": "weightb",
     "MIVC_HEVC_SLICES": "slices",
+    "MIVC_HEVC_TSKIP": "tskip",
+    "MIVC_HEVC_TSKIP_LAMBDA": "tskip_lambda",
 }
 # bench.py shape knobs (they change what is measured, so they also need --allow-knobs)
 # (MIVC_HIP_LIB: an alternative kernel library, tools/build_variant.py -- same-box A/B timing)

@@ -157,11 +157,51 @@ def random_records(rng, width: int, height: int, pslice: bool, bit_depth: int = 
     return ctu, cu, cy, cb, cr
 
 
+def coded_4x4_tus(ctu: np.ndarray, cu: np.ndarray, cy: np.ndarray, cb: np.ndarray, cr: np.ndarray) -> list:
+    """The coded 4x4 TUs of a picture's records, as (component, x, y) in the component's plane: the
+    luma PUs of PART_NxN intra CUs, the chroma blocks of 8x8 CUs and the chroma quarter TUs of
+    16x16 inter CUs whose residual quadtree splits -- each only where it holds a level."""
+    H, W = cy.shape
+    wc = W // CTB
+    out = []
+    for i in range(len(ctu)):
+        rx, ry = i % wc, i // wc
+        for (x, y, n) in _cu_list(int(ctu[i, 0])):
+            rec = cu[i * 16 + _zorder8(x // 8, y // 8)]
+            X, Y = rx * CTB + x, ry * CTB + y
+            cand = []
+            if n == 8:
+                if rec[0] == 0 and rec[3] & 8:
+                    cand += [(0, X + 4 * (k & 1), Y + 4 * (k >> 1)) for k in range(4)]
+                cand += [(1, X // 2, Y // 2), (2, X // 2, Y // 2)]
+            elif n == 16 and rec[0] == 1 and rec[3] & 16:
+                cand += [(c, X // 2 + 4 * (k & 1), Y // 2 + 4 * (k >> 1)) for c in (1, 2) for k in range(4)]
+            for c, px, py in cand:
+                if (cy, cb, cr)[c][py:py + 4, px:px + 4].any():
+                    out.append((c, px, py))
+    return out
+
+
+def tsmap_of(tus: list, width: int, height: int) -> np.ndarray:
+    """The writer's transform skip map (uint64 [CTBs, 2], laid out like pack_levels' nzmap) with
+    the bits of the 4x4 TUs ``tus`` = [(component, x, y)] set."""
+    W, H = -(-width // CTB) * CTB, -(-height // CTB) * CTB
+    ts = np.zeros((W // CTB * (H // CTB), 2), np.uint64)
+    for c, x, y in tus:
+        s = 1 if c else 0
+        ci = ((y << s) // CTB) * (W // CTB) + (x << s) // CTB
+        m, side = (15, 4) if c else (31, 8)
+        bit = ((y & m) >> 2) * side + ((x & m) >> 2) + (16 if c == 2 else 0)
+        ts[ci, 1 if c else 0] |= np.uint64(1 << bit)
+    return ts
+
+
 def random_stream(host, width: int, height: int, frames: int, seed: int = 0, qp: int = 30, bit_depth: int = 8,
-                  host_cfg: dict | None = None, qp_spread: int = 0, **kw) -> tuple[bytes, list]:
+                  host_cfg: dict | None = None, qp_spread: int = 0, tsmaps=None, **kw) -> tuple[bytes, list]:
     """Annex-B HEVC stream (IDR + P pictures) and the records it was written from.
     ``host_cfg`` adds writer options (e.g. ``wpp=1, threads=4``); ``qp_spread`` > 0 gives
-    every CTB its own QP (needs ``cu_qp_delta=1`` in ``host_cfg``)."""
+    every CTB its own QP (needs ``cu_qp_delta=1`` in ``host_cfg``); ``tsmaps``: a function of
+    (picture index, records) giving the picture's transform skip map or None (needs ``tskip=1``)."""
     rng = np.random.default_rng(seed)
     cfg = dict(width=width, height=height, bit_depth=bit_depth, **(host_cfg or {}))
     out = [host.hevc_parameter_sets(cfg)]
@@ -170,7 +210,8 @@ def random_stream(host, width: int, height: int, frames: int, seed: int = 0, qp:
         fqp = int(np.clip(qp + rng.integers(-3, 4), 0, 51))
         r = random_records(rng, width, height, pslice=t > 0, bit_depth=bit_depth,
                            ctb_qp=(fqp, qp_spread) if qp_spread else None, **kw)
-        nal, _ = host.hevc_write_slice(cfg, dict(idr=int(t == 0), poc=t, qp=fqp, slice_type=1 if t else 2), *r)
+        ts = {"tsmap": tsmaps(t, r)} if tsmaps is not None else {}
+        nal, _ = host.hevc_write_slice(cfg, dict(idr=int(t == 0), poc=t, qp=fqp, slice_type=1 if t else 2), *r, **ts)
         out.append(nal)
         recs.append(r)
     return b"".join(out), recs
@@ -178,7 +219,8 @@ def random_stream(host, width: int, height: int, frames: int, seed: int = 0, qp:
 
 def random_gop_stream(host, width: int, height: int, frames: int, bframes: int = 3, seed: int = 0, qp: int = 30,
                       bit_depth: int = 8, tmvp: bool = True, pyramid: bool = False, host_cfg: dict | None = None,
-                      refs: int = 1, weights: dict | None = None, b_residual: bool = True, **kw) -> tuple[bytes, list]:
+                      refs: int = 1, weights: dict | None = None, b_residual: bool = True, tsmaps=None,
+                      **kw) -> tuple[bytes, list]:
     """Annex-B HEVC stream of one closed GOP with B pictures (models/gop.py hevc_gop_plan:
     I, P anchors, B pictures referencing the pictures on both sides; ``pyramid``: the middle
     B of a run is a reference picture) from random records, with each picture's RPS; TMVP
@@ -188,7 +230,8 @@ def random_gop_stream(host, width: int, height: int, frames: int, bframes: int =
     ``weights``: display index -> dict of the picture's explicit weights (``wp`` for list 0, ``wp1``
     for list 1 of a B picture, each [w, o] x (Y, Cb, Cr); needs ``weightp`` / ``weightb`` in
     ``host_cfg``); ``b_residual`` False: B pictures carry no levels (their decoded samples are
-    the prediction)."""
+    the prediction); ``tsmaps``: a function of (display index, records) giving the picture's
+    transform skip map or None (needs ``tskip=1`` in ``host_cfg``)."""
     from ..models.gop import hevc_gop_plan, hevc_ref_slots
 
     rng = np.random.default_rng(seed)
@@ -215,7 +258,8 @@ def random_gop_stream(host, width: int, height: int, frames: int, bframes: int =
                 fp["ref_poc1"] = pic.l1
             ccu, c0, c1, cl0 = held[col]
             fp.update(col_poc=col, col_ref_poc0=c0, col_ref_poc1=c1, col_cu=ccu, col_refs0=cl0)
-        nal, _ = host.hevc_write_slice(cfg, fp, *r)
+        ts = {"tsmap": tsmaps(pic.d, r)} if tsmaps is not None else {}
+        nal, _ = host.hevc_write_slice(cfg, fp, *r, **ts)
         if pic.ref:
             held[pic.d] = (None if pic.kind == "I" else r[1].copy(), pic.l0, pic.l1, list(pic.refs0) or None)
         out.append(nal)

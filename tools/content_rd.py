@@ -151,6 +151,11 @@ HEVC_CONFIGS = {
     # x265 --slices: independent slices per picture (profiles/hevc_slices.md)
     "slices2": dict(slices=2),
     "slices4": dict(slices=4),
+    # x265 --tskip: transform skip for 4x4 TUs and its lambda multiplier (profiles/hevc_tskip.md)
+    "tskip": dict(tskip=True),
+    "tskip_l050": dict(tskip=True, tskip_lambda=0.5),
+    "tskip_l200": dict(tskip=True, tskip_lambda=2.0),
+    "tskip_rdoq2": dict(tskip=True, rdoq_level=2, rdoq_lambda=0.5),
 }
 
 
@@ -171,6 +176,10 @@ def run(args):
         make = lambda over: GpuH264Encoder(H264Params(width=w, height=h, **over), slots=args.slots)  # noqa: E731
     clips = {}
     for kind in kinds:
+        if kind == "screen":  # text / UI / line art (utils/screen_synth.py): not one of CONTENT_KINDS
+            from govideocompressor_amd.utils.screen_synth import screen_clip
+            clips[kind] = screen_clip(args.slots, args.frames, w, h, seed=17)
+            continue
         clips[kind] = synth_clip(args.slots, args.frames, w, h, seed=17, kind=kind)
     for cname, over in configs.items():
         enc = make(over)
@@ -196,6 +205,8 @@ def run(args):
                           direct_unavail_ratio=stats.get("direct_unavail_ratio"))
                 if "weightb_pictures" in stats:
                     pt["weightb_pictures"] = stats["weightb_pictures"]
+                if "tskip_tus" in stats:  # 4x4 TUs coded with transform_skip_flag 1: intra luma, intra chroma, inter chroma
+                    pt["tskip_tus"] = list(stats["tskip_tus"])
                 if getattr(enc, "stage_ms", None):  # MIVC_STAGE_TIMING=1: device time per stage of this call
                     pt["stage_ms"] = dict(enc.stage_ms)
                 out["points"].append(pt)
