@@ -39,7 +39,8 @@ MIVC_HD bool chroma_mode_ok(int mode, int av) {  // 0 DC, 1 H, 2 V, 3 Plane
 }
 
 // e[0] = p[-1,-1], e[1..8] = p[0..7,-1] (top + top-right, already substituted), e[9..12] = p[-1,0..3]
-MIVC_HD int i4_pred_sample(int mode, int av, const int* e, int x, int y) {
+// half = 1 << (BitDepth - 1), here and below: the DC prediction without neighbours
+MIVC_HD int i4_pred_sample(int mode, int av, const int* e, int x, int y, int half = 128) {
   const int* T = e + 1;   // T[-1] == top-left
   const int* L = e + 9;
   auto l = [&](int i) { return i < 0 ? e[0] : L[i]; };
@@ -60,7 +61,7 @@ MIVC_HD int i4_pred_sample(int mode, int av, const int* e, int x, int y) {
         for (int i = 0; i < 4; ++i) s += T[i];
         return (s + 2) >> 2;
       }
-      return 128;
+      return half;
     }
     case 3:
       if (x == 3 && y == 3) return (T[6] + 3 * T[7] + 2) >> 2;
@@ -109,7 +110,7 @@ MIVC_HD void i16_plane_params(const T* top, const T* left, int tl, int* a, int* 
   *c = (5 * V + 32) >> 6;
 }
 template <class T>
-MIVC_HD int i16_dc(const T* top, const T* left, int av) {
+MIVC_HD int i16_dc(const T* top, const T* left, int av, int half = 128) {
   int st = 0, sl = 0;
   for (int i = 0; i < 16; ++i) {
     st += top[i];
@@ -118,12 +119,12 @@ MIVC_HD int i16_dc(const T* top, const T* left, int av) {
   if ((av & AV_TOP) && (av & AV_LEFT)) return (st + sl + 16) >> 5;
   if (av & AV_LEFT) return (sl + 8) >> 4;
   if (av & AV_TOP) return (st + 8) >> 4;
-  return 128;
+  return half;
 }
 
 // chroma 8x8 (4:2:0) DC for 4x4 block (bx,by)
 template <class T>
-MIVC_HD int chroma_dc(const T* top, const T* left, int av, int bx, int by) {
+MIVC_HD int chroma_dc(const T* top, const T* left, int av, int bx, int by, int half = 128) {
   int st = 0, sl = 0;
   for (int i = 0; i < 4; ++i) {
     st += top[bx * 4 + i];
@@ -134,16 +135,16 @@ MIVC_HD int chroma_dc(const T* top, const T* left, int av, int bx, int by) {
     if (t && l) return (st + sl + 4) >> 3;
     if (l) return (sl + 2) >> 2;
     if (t) return (st + 2) >> 2;
-    return 128;
+    return half;
   }
   if (bx == 1) {  // top-right block
     if (t) return (st + 2) >> 2;
     if (l) return (sl + 2) >> 2;
-    return 128;
+    return half;
   }
   if (l) return (sl + 2) >> 2;  // bottom-left block
   if (t) return (st + 2) >> 2;
-  return 128;
+  return half;
 }
 template <class T>
 MIVC_HD void chroma_plane_params(const T* top, const T* left, int tl, int* a, int* b, int* c) {
@@ -205,23 +206,9 @@ MIVC_HD int mc_luma_sample(const P& ref, int xi, int yi, int xf, int yf) {
 }
 
 // ---------------------------------------------------------------- samples of more than 8 bits
-// Overloads for BitDepth 9..14 (High 10 and up): maxv = (1 << BitDepth) - 1 bounds the clips
-// and half = 1 << (BitDepth - 1) is the DC prediction without neighbours.  The 8-bit
-// functions above are maxv = 255, half = 128.
+// Overloads for BitDepth 9..14 (High 10 and up): maxv = (1 << BitDepth) - 1 bounds the clips.
+// The 8-bit functions above are maxv = 255.
 MIVC_HD int clip1(int v, int maxv) { return v < 0 ? 0 : (v > maxv ? maxv : v); }
-
-MIVC_HD int i4_pred_sample(int mode, int av, const int* e, int x, int y, int half) {
-  if (mode == 2 && !(av & (AV_TOP | AV_LEFT))) return half;
-  return i4_pred_sample(mode, av, e, x, y);
-}
-template <class T>
-MIVC_HD int i16_dc(const T* top, const T* left, int av, int half) {
-  return (av & (AV_TOP | AV_LEFT)) ? i16_dc(top, left, av) : half;
-}
-template <class T>
-MIVC_HD int chroma_dc(const T* top, const T* left, int av, int bx, int by, int half) {
-  return (av & (AV_TOP | AV_LEFT)) ? chroma_dc(top, left, av, bx, by) : half;
-}
 
 template <class P>
 MIVC_HD int mc_luma_sample(const P& ref, int xi, int yi, int xf, int yf, int maxv) {

@@ -170,6 +170,13 @@ static constexpr uint8_t kInterCbpToCode[48] = {0, 2, 3, 7, 4, 8, 17, 13, 5, 18,
 MIVC_HD int clip3(int lo, int hi, int v) { return v < lo ? lo : (v > hi ? hi : v); }
 MIVC_HD int clip1(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 MIVC_HD int chroma_qp(int qpy, int offset) { return kChromaQp[clip3(0, 51, qpy + offset)]; }
+// QPC for chroma samples of more than 8 bits (8.5.8): qPI = Clip3(-QpBdOffsetC, 51, QPY + offset),
+// Table 8-15 from 0 up, qPI itself below; QP'C = QPC + QpBdOffsetC is the caller's.  qpbd = 0 is
+// chroma_qp.
+MIVC_HD int chroma_qp_bd(int qpy, int offset, int qpbd) {
+  const int qpi = clip3(-qpbd, 51, qpy + offset);
+  return qpi < 0 ? qpi : static_cast<int>(kChromaQp[qpi]);
+}
 
 // 6-tap half-sample filter tap sum (clause 8.4.2.2.1): E - 5F + 20G + 20H - 5I + J
 MIVC_HD int tap6(int e, int f, int g, int h, int i, int j) { return e - 5 * f + 20 * g + 20 * h - 5 * i + j; }

@@ -51,12 +51,6 @@ struct Deblock16Shared {
   int par[2][2][2][5];   // [dir][mb edge / inner][luma / chroma]: alpha, beta, tc0 for bS 1..3
 };
 
-// QPC of a macroblock for the filter (8.7.2.2 with 8.5.8): no bit-depth offset added
-__device__ __forceinline__ int dbk16_qpc(int qpy, int offset, int qpbd) {
-  const int qpi = clampi(qpy + offset, -qpbd, 51);
-  return qpi < 0 ? qpi : static_cast<int>(h264::kChromaQp[qpi]);
-}
-
 // filter one line across an edge (8.7.2.3 / 8.7.2.4); q0 points at q0, step = distance p0 -> q0
 __device__ __forceinline__ void dbk16_line(uint16_t* q0p, int step, int bs, int alpha, int beta, int tc0, bool chroma,
                                            int maxv) {
@@ -156,9 +150,9 @@ __global__ __launch_bounds__(64 * kDeblock16Waves) void deblock16_wavefront(Debl
         const int i = lane - 32, dir = i >> 2, inner = (i >> 1) & 1, ch = i & 1;
         const int nb = dir == 0 ? (has_left ? mb - 1 : mb) : (has_top ? mb - wmb : mb);
         int qq = hdr[mb].qp, qn = inner ? qq : static_cast<int>(hdr[nb].qp);
-        if (ch) {
-          qq = dbk16_qpc(qq, a.chroma_qp_offset, qpbd);
-          qn = dbk16_qpc(qn, a.chroma_qp_offset, qpbd);
+        if (ch) {  // QPC of the two MBs (8.7.2.2 with 8.5.8): no bit-depth offset added
+          qq = h264::chroma_qp_bd(qq, a.chroma_qp_offset, qpbd);
+          qn = h264::chroma_qp_bd(qn, a.chroma_qp_offset, qpbd);
         }
         const int qpav = (qq + qn + 1) >> 1;
         const int ia = clampi(qpav + a.alpha_off, 0, 51), ib = clampi(qpav + a.beta_off, 0, 51);

@@ -19,7 +19,15 @@
 //    filtering, 9 modes) and Intra16x16; all MBs of an I picture, only the intra MBs of a
 //    P / B picture (their inter neighbours are final);
 //  * the in-loop filter is the encoder's deblock kernel (deblock.hip) reading the parser's
-//    boundary strengths.
+//    boundary strengths (deblock16.hip for 16-bit planes).
+//
+// One source, two instantiations: 8-bit samples in uint8_t planes (the two kernels above)
+// and High 10 samples (BitDepthY == BitDepthC in {9, 10}) in uint16_t planes
+// (decode_inter_dpb16, decode_intra_wavefront16).  Records, level pool, reference tables
+// and launch shapes are the same.  The code is written for a depth policy D: bd() bits,
+// clips to maxv() = (1 << bd) - 1, DC prediction without neighbours half() = 1 << (bd - 1),
+// QpBdOffset qpbd() = 6 * (bd - 8).  For 8 bits these are constants and fold away; what is
+// left per depth is how samples pack into dwords (stage_row, store4).
 //
 // Reference parity: the reference decodes with ffmpeg inside the worker
 // (client.go:115-118); the CPU decoder (h264_decoder.cc) is the bit-exact oracle.
@@ -31,9 +39,90 @@ namespace gpu {
 
 using h264::MbHeader;
 
-struct DecodeArgs {
+// ============================================================== sample depth
+// two samples (each below 1 << 16) in one dword, first in the low half, by v_perm_b32 (see
+// pack4_u8 in kcommon.h on shift / or packing of clipped values)
+__device__ __forceinline__ uint32_t pack2(int lo, int hi) {
+  return __builtin_amdgcn_perm(static_cast<uint32_t>(hi), static_cast<uint32_t>(lo), 0x05040100u);
+}
+
+struct Depth8 {
+  using Pix = uint8_t;
+  __device__ static constexpr int bd() { return 8; }
+  __device__ static constexpr int maxv() { return 255; }
+  __device__ static constexpr int half() { return 128; }
+  __device__ static constexpr int qpbd() { return 0; }
+
+  // 13 samples of a reference row from x0 on (clamped: unrestricted vectors, 8.4.2.2.1) into
+  // one 16-byte row of the LDS window
+  __device__ static __forceinline__ void stage_row(const uint8_t* row, int x0, int W, uint32_t* dst) {
+    if (x0 >= 0 && x0 + 16 <= W) {  // inside the row: four aligned dwords cover the 13 bytes
+      const int xa = x0 & ~3, sh = x0 & 3;
+      const uint32_t* s4 = reinterpret_cast<const uint32_t*>(row + xa);
+      const uint32_t e0 = s4[0], e1 = s4[1], e2 = s4[2], e3 = s4[3];
+      dst[0] = __builtin_amdgcn_alignbyte(e1, e0, sh);
+      dst[1] = __builtin_amdgcn_alignbyte(e2, e1, sh);
+      dst[2] = __builtin_amdgcn_alignbyte(e3, e2, sh);
+      dst[3] = __builtin_amdgcn_alignbyte(0u, e3, sh);  // byte 12 (the last one used) lies in e3
+    } else {
+      uint32_t w4[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) v |= static_cast<uint32_t>(row[clampi(x0 + 4 * k + b, 0, W - 1)]) << (8 * b);
+        w4[k] = v;
+      }
+      dst[0] = w4[0];
+      dst[1] = w4[1];
+      dst[2] = w4[2];
+      dst[3] = w4[3];
+    }
+  }
+  // four samples (each 0 .. 255) as one dword store
+  __device__ static __forceinline__ void store4(uint8_t* dst, const int* p) {
+    *reinterpret_cast<uint32_t*>(dst) = static_cast<uint32_t>(p[0]) | static_cast<uint32_t>(p[1]) << 8 |
+                                        static_cast<uint32_t>(p[2]) << 16 | static_cast<uint32_t>(p[3]) << 24;
+  }
+};
+
+struct DepthHi {
+  using Pix = uint16_t;
+  int bits;  // BitDepthY == BitDepthC (9 or 10)
+  __device__ __forceinline__ int bd() const { return bits; }
+  __device__ __forceinline__ int maxv() const { return (1 << bits) - 1; }
+  __device__ __forceinline__ int half() const { return 1 << (bits - 1); }
+  __device__ __forceinline__ int qpbd() const { return 6 * (bits - 8); }
+
+  // as Depth8::stage_row, into one 32-byte row of the LDS window
+  __device__ static __forceinline__ void stage_row(const uint16_t* row, int x0, int W, uint32_t* dst) {
+    if (x0 >= 0 && x0 + 14 <= W) {
+      // inside the row: seven aligned dwords (samples xa .. xa + 13) cover the 13 samples,
+      // shifted by the odd sample of a 2-sample granule
+      const int xa = x0 & ~1, sh = (x0 & 1) * 2;
+      const uint32_t* s2 = reinterpret_cast<const uint32_t*>(row + xa);
+      uint32_t e[8];
+#pragma unroll
+      for (int k = 0; k < 7; ++k) e[k] = s2[k];
+      e[7] = 0u;  // sample 12 (the last one used) lies in e[6]
+#pragma unroll
+      for (int k = 0; k < 7; ++k) dst[k] = __builtin_amdgcn_alignbyte(e[k + 1], e[k], sh);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 7; ++k)
+        dst[k] = pack2(row[clampi(x0 + 2 * k, 0, W - 1)], row[clampi(x0 + 2 * k + 1, 0, W - 1)]);
+    }
+  }
+  // four samples as one 8-byte store
+  __device__ static __forceinline__ void store4(uint16_t* dst, const int* p) {
+    *reinterpret_cast<uint2*>(dst) = make_uint2(pack2(p[0], p[1]), pack2(p[2], p[3]));
+  }
+};
+
+template <class Pix>
+struct DecodeFields {
   Geom g;
-  uint8_t *rec_y, *rec_u, *rec_v;        // decoded picture buffers (see dpb_n)
+  Pix *rec_y, *rec_u, *rec_v;            // decoded picture buffers (see dpb_n)
   const MbHeader* hdr;                   // [B, nmb]
   const uint32_t* mask;                  // [B, nmb] present blocks
   const uint32_t* off;                   // [B, nmb] first block (units of 16 levels, into coef)
@@ -52,6 +141,20 @@ struct DecodeArgs {
   // (h264::kSubEntry int16 per entry, indices already global to the batch step)
   const int16_t* sub;
 };
+// the kernels' argument: the fields, then what the depth keeps (nothing for 8 bits, so the
+// 8-bit kernels' argument layout is the fields alone)
+template <class D>
+struct DecodeArgs : DecodeFields<typename D::Pix>, D {};
+static_assert(sizeof(DecodeArgs<Depth8>) == sizeof(DecodeFields<uint8_t>), "no depth field in the 8-bit arguments");
+
+// MbHeader::qp is QPY in -QpBdOffset .. 51: luma dequantises with QP'Y = QPY + QpBdOffsetY
+// (8.5.12.1), chroma with QP'C = QPC + QpBdOffsetC (8.5.8); every % 6 and / 6 comes after
+template <class D>
+__device__ __forceinline__ int luma_qp(const D& d, int qpy) { return qpy + d.qpbd(); }
+template <class D>
+__device__ __forceinline__ int chroma_qp(const D& d, int qpy, int offset) {
+  return h264::chroma_qp_bd(qpy, offset, d.qpbd()) + d.qpbd();
+}
 
 // weighted-prediction table layout (mirrors mivc::h264::kWp* in h264_decoder.h)
 enum : int { kWpLw = 4, kWpLo = 68, kWpCw = 132, kWpCo = 260, kWpImp = 388, kWpScale = 516, kWpFlags = 740,
@@ -65,13 +168,14 @@ struct Scaling {
   __device__ __forceinline__ int w4(int li, int x, int y) const { return t ? t[li * 16 + y * 4 + x] : 16; }
   __device__ __forceinline__ int w8(int li, int x, int y) const { return t ? t[96 + li * 64 + y * 8 + x] : 16; }
 };
-__device__ __forceinline__ Scaling scaling_of(const DecodeArgs& a, int slot) {
-  return Scaling{a.wp ? a.wp + static_cast<size_t>(slot) * kWpEntries + kWpScale : nullptr};
+__device__ __forceinline__ Scaling scaling_of(const int16_t* wp, int slot) {
+  return Scaling{wp ? wp + static_cast<size_t>(slot) * kWpEntries + kWpScale : nullptr};
 }
 
 // the picture being reconstructed (luma / chroma plane) of a slot
-__device__ __forceinline__ uint8_t* rec_plane(const DecodeArgs& a, uint8_t* base, int slot, size_t psize) {
-  if (a.dpb_n == 0) return base + static_cast<size_t>(slot) * psize;
+template <class D>
+__device__ __forceinline__ typename D::Pix* rec_plane(const DecodeArgs<D>& a, typename D::Pix* base, int slot,
+                                                      size_t psize) {
   return base + (static_cast<size_t>(slot) * a.dpb_n + a.cur_idx[slot]) * psize;
 }
 
@@ -115,11 +219,6 @@ __device__ __forceinline__ int chroma_dc_value(const int16_t* coef, uint32_t mas
   return ((f * ls) << (qpc / 6)) >> 5;
 }
 
-__device__ __forceinline__ uint32_t pack4(const int* p) {
-  return static_cast<uint32_t>(p[0]) | static_cast<uint32_t>(p[1]) << 8 | static_cast<uint32_t>(p[2]) << 16 |
-         static_cast<uint32_t>(p[3]) << 24;
-}
-
 // ============================================================== inter macroblocks, DPB layout
 // Every P / B macroblock of every slot in parallel (one wave64 per MB): per raster 4x4
 // block and list its own vector and reference picture (sub-8x8 partitions, B_8x8, direct
@@ -141,12 +240,12 @@ __device__ __forceinline__ int level_scale8(int m, int x, int y, int w) {
   return w * t[m][k];
 }
 
-// one 8-point pass of the 8x8 inverse transform (8.5.13.2), in place, stride s
-
 // weighted sample prediction of one sample (8.4.2.3); r0 / r1 = ref_idx (-1: list unused)
-__device__ __forceinline__ int weigh(const int16_t* w, bool chroma, int comp, int r0, int r1, int p0, int p1) {
+template <class D>
+__device__ __forceinline__ int weigh(const D& d, const int16_t* w, bool chroma, int comp, int r0, int r1, int p0, int p1) {
   const int mode = w[0];
   const bool b0 = r0 >= 0, b1 = r1 >= 0;
+  const int maxv = d.maxv();
   if (mode == 1) {
     const int logwd = chroma ? w[2] : w[1];
     int w0 = 0, o0 = 0, w1 = 0, o1 = 0;
@@ -158,14 +257,16 @@ __device__ __forceinline__ int weigh(const int16_t* w, bool chroma, int comp, in
       w1 = chroma ? w[kWpCw + (32 + r1) * 2 + comp] : w[kWpLw + 32 + r1];
       o1 = chroma ? w[kWpCo + (32 + r1) * 2 + comp] : w[kWpLo + 32 + r1];
     }
-    if (b0 && b1) return h264::clip1(((p0 * w0 + p1 * w1 + (1 << logwd)) >> (logwd + 1)) + ((o0 + o1 + 1) >> 1));
+    o0 *= 1 << (d.bd() - 8);  // the table's offsets count in units of the 8-bit range (8.4.2.3.2)
+    o1 *= 1 << (d.bd() - 8);
+    if (b0 && b1) return h264::clip1(((p0 * w0 + p1 * w1 + (1 << logwd)) >> (logwd + 1)) + ((o0 + o1 + 1) >> 1), maxv);
     const int p = b0 ? p0 : p1, ww = b0 ? w0 : w1, o = b0 ? o0 : o1;
-    return h264::clip1(logwd >= 1 ? ((p * ww + (1 << (logwd - 1))) >> logwd) + o : p * ww + o);
+    return h264::clip1(logwd >= 1 ? ((p * ww + (1 << (logwd - 1))) >> logwd) + o : p * ww + o, maxv);
   }
   if (b0 && b1) {
     if (mode == 2) {
       const int w0 = w[kWpImp + ((r0 & 7) * 8 + (r1 & 7)) * 2], w1 = w[kWpImp + ((r0 & 7) * 8 + (r1 & 7)) * 2 + 1];
-      return h264::clip1((p0 * w0 + p1 * w1 + 32) >> 6);
+      return h264::clip1((p0 * w0 + p1 * w1 + 32) >> 6, maxv);
     }
     return (p0 + p1 + 1) >> 1;
   }
@@ -174,7 +275,9 @@ __device__ __forceinline__ int weigh(const int16_t* w, bool chroma, int comp, in
 
 constexpr int kBW = 9;  // 4x4 block + 6-tap support (-2 .. +6)
 
-__global__ __launch_bounds__(64) void decode_inter_dpb(DecodeArgs a) {
+template <class D>
+__device__ __forceinline__ void decode_inter_mb(const DecodeArgs<D>& a) {
+  using Pix = typename D::Pix;
   const Geom& g = a.g;
   int mb, slot;
   xcd_unit_slot(mb, slot);
@@ -184,19 +287,20 @@ __global__ __launch_bounds__(64) void decode_inter_dpb(DecodeArgs a) {
   if (h264::mbk_is_intra(H->kind)) return;
   // reference windows: per (list, 4x4 block) 9x9 when the MB carries sub-8x8 motion, else per
   // (list, 8x8 quadrant) 13x13 (one vector per quadrant: the four blocks' windows overlap)
-  // in rows of kQP bytes, staged a row per lane with dword loads
+  // in rows of kQP samples, staged a row per lane with dword loads
   constexpr int kQP = 16, kQW = 13;
-  __shared__ __attribute__((aligned(16))) uint8_t win[2][16][kBW * kBW];
+  __shared__ __attribute__((aligned(16))) Pix win[2][16][kBW * kBW];
   __shared__ int d8[4][64];
   const int lane = threadIdx.x;
   const int mx = mb % g.wmb, my = mb / g.wmb;
   const int W = g.W, Hh = g.H, cw = g.cw(), ch = g.ch();
   const int X0 = mx * 16, Y0 = my * 16;
-  const int qp = H->qp;
-  const int qpc = h264::chroma_qp(qp, a.chroma_qp_offset);
+  const int maxv = a.maxv();
+  const int qp = luma_qp(a, H->qp);
+  const int qpc = chroma_qp(a, H->qp, a.chroma_qp_offset);
   const uint32_t mask = a.mask[o], off = a.off[o];
   const bool t8 = (H->flags & h264::MBF_T8x8) != 0;
-  const int D = a.dpb_n;
+  const int nd = a.dpb_n;
   const int nmb = g.nmb();
   const int16_t* rt = a.reftab + slot * 64;
   const bool sub4 = (H->flags & h264::MBF_SUB4) != 0;
@@ -207,7 +311,7 @@ __global__ __launch_bounds__(64) void decode_inter_dpb(DecodeArgs a) {
     se = a.sub + static_cast<size_t>(si) * h264::kSubEntry;
   }
   const int16_t* wt = a.wp + static_cast<size_t>(slot) * kWpEntries;
-  const Scaling sc = scaling_of(a, slot);
+  const Scaling sc = scaling_of(a.wp, slot);
   auto quad = [](int rb) { return ((rb & 3) >> 1) + 2 * (rb >> 3); };
   auto mv_of = [&](int l, int rb, int c) {
     return static_cast<int>(sub4 ? se[(l * 16 + rb) * 2 + c] : H->mv[l][quad(rb)][c]);
@@ -217,7 +321,7 @@ __global__ __launch_bounds__(64) void decode_inter_dpb(DecodeArgs a) {
   };
   auto pic_of = [&](int l, int r) {  // DPB index of RefPicListl[r], validated
     const int di = (r >= 0 && r < 32) ? rt[l * 32 + r] : -1;
-    if (di < 0 || di >= D) {
+    if (di < 0 || di >= nd) {
       atomicOr(a.err, 16);
       return 0;
     }
@@ -225,7 +329,7 @@ __global__ __launch_bounds__(64) void decode_inter_dpb(DecodeArgs a) {
   };
 
   // ---- stage the reference windows (clamped: unrestricted vectors)
-  uint8_t* qwin = &win[0][0][0];  // quadrant mode: [l][q][kQW rows][kQP] inside the same storage
+  Pix* qwin = &win[0][0][0];  // quadrant mode: [l][q][kQW rows][kQP] inside the same storage
   static_assert(2 * 4 * kQW * kQP <= 2 * 16 * kBW * kBW, "quadrant windows fit the block windows' storage");
   if (sub4) {
     for (int i = lane; i < 2 * 16 * kBW * kBW; i += 64) {
@@ -237,7 +341,7 @@ __global__ __launch_bounds__(64) void decode_inter_dpb(DecodeArgs a) {
       const int rr = j / kBW, cc = j - rr * kBW;
       const int x = clampi(X0 + (rb & 3) * 4 + (mv_of(l, rb, 0) >> 2) - 2 + cc, 0, W - 1);
       const int y = clampi(Y0 + (rb >> 2) * 4 + (mv_of(l, rb, 1) >> 2) - 2 + rr, 0, Hh - 1);
-      win[l][rb][j] = a.rec_y[(static_cast<size_t>(slot) * D + di) * g.ysize() + static_cast<size_t>(y) * W + x];
+      win[l][rb][j] = a.rec_y[(static_cast<size_t>(slot) * nd + di) * g.ysize() + static_cast<size_t>(y) * W + x];
     }
   } else {
     for (int i = lane; i < 2 * 4 * kQW; i += 64) {  // one window row per lane
@@ -248,30 +352,8 @@ __global__ __launch_bounds__(64) void decode_inter_dpb(DecodeArgs a) {
       const int di = pic_of(l, r);
       const int x0 = X0 + (q & 1) * 8 + (H->mv[l][q][0] >> 2) - 2;
       const int y = clampi(Y0 + (q >> 1) * 8 + (H->mv[l][q][1] >> 2) - 2 + rr, 0, Hh - 1);
-      const uint8_t* row = a.rec_y + (static_cast<size_t>(slot) * D + di) * g.ysize() + static_cast<size_t>(y) * W;
-      uint32_t* dst = reinterpret_cast<uint32_t*>(qwin + ((l * 4 + q) * kQW + rr) * kQP);
-      if (x0 >= 0 && x0 + 16 <= W) {  // inside the row: four aligned dwords cover the 13 bytes
-        const int xa = x0 & ~3, sh = x0 & 3;
-        const uint32_t* s4 = reinterpret_cast<const uint32_t*>(row + xa);
-        const uint32_t e0 = s4[0], e1 = s4[1], e2 = s4[2], e3 = s4[3];
-        dst[0] = __builtin_amdgcn_alignbyte(e1, e0, sh);
-        dst[1] = __builtin_amdgcn_alignbyte(e2, e1, sh);
-        dst[2] = __builtin_amdgcn_alignbyte(e3, e2, sh);
-        dst[3] = __builtin_amdgcn_alignbyte(0u, e3, sh);  // byte 12 (the last one used) lies in e3
-      } else {
-        uint32_t w4[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          uint32_t v = 0;
-#pragma unroll
-          for (int b = 0; b < 4; ++b) v |= static_cast<uint32_t>(row[clampi(x0 + 4 * k + b, 0, W - 1)]) << (8 * b);
-          w4[k] = v;
-        }
-        dst[0] = w4[0];
-        dst[1] = w4[1];
-        dst[2] = w4[2];
-        dst[3] = w4[3];
-      }
+      const Pix* row = a.rec_y + (static_cast<size_t>(slot) * nd + di) * g.ysize() + static_cast<size_t>(y) * W;
+      D::stage_row(row, x0, W, reinterpret_cast<uint32_t*>(qwin + ((l * 4 + q) * kQW + rr) * kQP));
     }
   }
   // ---- 8x8 transform: dequantise (lane = b8 * 16 + t, four levels each), then row and
@@ -308,11 +390,11 @@ __global__ __launch_bounds__(64) void decode_inter_dpb(DecodeArgs a) {
       const int r = l ? r1 : r0;
       const int fx = mv_of(l, rb, 0) & 3, fy = mv_of(l, rb, 1) & 3;
       // this block's 9x9 window: its own (sub-8x8 motion) or inside its quadrant's 13x13
-      const uint8_t* w = sub4 ? win[l][rb] : qwin + (l * 4 + quad(rb)) * kQW * kQP + (by & 1) * 4 * kQP + (bx & 1) * 4;
+      const Pix* w = sub4 ? win[l][rb] : qwin + (l * 4 + quad(rb)) * kQW * kQP + (by & 1) * 4 * kQP + (bx & 1) * 4;
       const int pitch = sub4 ? kBW : kQP;
       auto ref = [&](int x, int y) { return static_cast<int>(w[(y + 2) * pitch + x + 2]); };
 #pragma unroll
-      for (int x = 0; x < 4; ++x) pl[l][x] = r >= 0 ? h264::mc_luma_sample(ref, x, gy, fx, fy) : 0;
+      for (int x = 0; x < 4; ++x) pl[l][x] = r >= 0 ? h264::mc_luma_sample(ref, x, gy, fx, fy, maxv) : 0;
     }
     int v[4], pr[4];
     if (t8) {
@@ -327,9 +409,9 @@ __global__ __launch_bounds__(64) void decode_inter_dpb(DecodeArgs a) {
       grp_inv4x4(v, lane & ~3, gy);
     }
 #pragma unroll
-    for (int x = 0; x < 4; ++x) pr[x] = h264::clip1(weigh(wt, false, 0, r0, r1, pl[0][x], pl[1][x]) + v[x]);
-    uint8_t* recy = rec_plane(a, a.rec_y, slot, g.ysize());
-    *reinterpret_cast<uint32_t*>(recy + static_cast<size_t>(Y0 + by * 4 + gy) * W + X0 + bx * 4) = pack4(pr);
+    for (int x = 0; x < 4; ++x) pr[x] = h264::clip1(weigh(a, wt, false, 0, r0, r1, pl[0][x], pl[1][x]) + v[x], maxv);
+    Pix* recy = rec_plane(a, a.rec_y, slot, g.ysize());
+    D::store4(recy + static_cast<size_t>(Y0 + by * 4 + gy) * W + X0 + bx * 4, pr);
     if (lane < 16) a.nz[o * 16 + blk_x(lane) + 4 * blk_y(lane)] = (mask >> lane) & 1u;
   }
   // ---- chroma: (lane & 31) = comp * 16 + block * 4 + row; every chroma sample takes the
@@ -351,7 +433,7 @@ __global__ __launch_bounds__(64) void decode_inter_dpb(DecodeArgs a) {
         pc[l] = 0;
         if (r >= 0) {
           const int di = pic_of(l, r);
-          const uint8_t* refc = (comp == 0 ? a.rec_u : a.rec_v) + (static_cast<size_t>(slot) * D + di) * g.csize();
+          const Pix* refc = (comp == 0 ? a.rec_u : a.rec_v) + (static_cast<size_t>(slot) * nd + di) * g.csize();
           const int cmx = mv_of(l, rb, 0), cmy = mv_of(l, rb, 1);
           const int xf = cmx & 7, yf = cmy & 7;
           const int xi = mx * 8 + Xc + (cmx >> 3), yi = my * 8 + Yc + (cmy >> 3);
@@ -362,19 +444,22 @@ __global__ __launch_bounds__(64) void decode_inter_dpb(DecodeArgs a) {
           pc[l] = ((8 - xf) * (8 - yf) * A + xf * (8 - yf) * Bv + (8 - xf) * yf * C + xf * yf * Dv + 32) >> 6;
         }
       }
-      pr[x] = weigh(wt, true, comp, r0, r1, pc[0], pc[1]);
+      pr[x] = weigh(a, wt, true, comp, r0, r1, pc[0], pc[1]);
     }
     dequant_row(a.coef, mask, off, 18 + comp * 4 + cb, gy, qpc, true, v, sc, 4 + comp);
     if (gy == 0) v[0] = chroma_dc_value(a.coef, mask, off, comp, cb, qpc, sc.w4(4 + comp, 0, 0));
     grp_inv4x4(v, lane & ~3, gy);
 #pragma unroll
-    for (int x = 0; x < 4; ++x) pr[x] = h264::clip1(pr[x] + v[x]);
+    for (int x = 0; x < 4; ++x) pr[x] = h264::clip1(pr[x] + v[x], maxv);
     if (lane < 32) {
-      uint8_t* recc = rec_plane(a, comp == 0 ? a.rec_u : a.rec_v, slot, g.csize());
-      *reinterpret_cast<uint32_t*>(recc + static_cast<size_t>(my * 8 + Yc) * cw + mx * 8 + cbx) = pack4(pr);
+      Pix* recc = rec_plane(a, comp == 0 ? a.rec_u : a.rec_v, slot, g.csize());
+      D::store4(recc + static_cast<size_t>(my * 8 + Yc) * cw + mx * 8 + cbx, pr);
     }
   }
 }
+
+__global__ __launch_bounds__(64) void decode_inter_dpb(DecodeArgs<Depth8> a) { decode_inter_mb(a); }
+__global__ __launch_bounds__(64) void decode_inter_dpb16(DecodeArgs<DepthHi> a) { decode_inter_mb(a); }
 
 // ============================================================== intra macroblocks
 // Intra4x4 neighbour availability of block b (top-right per 6.4.11.4 / the blkIdx order)
@@ -397,27 +482,29 @@ __device__ __forceinline__ int i4_avail(int b, int mbav) {
 constexpr int kDecIntraWaves = 8;
 constexpr int TS = kTileStride;
 
+template <class Pix>
 struct DecIntraShared {
-  uint8_t tile[17 * TS];            // luma: row 0 / col 0 = reconstructed neighbours
-  int16_t res[16][16];              // Intra4x4 residual per blkIdx (raster)
-  int e4[16];                       // Intra4x4 neighbour vector of the current block
-  int lv16dc[16];                   // Intra16x16 DC after the inverse Hadamard + scaling (raster)
-  uint8_t ctop[2][9], cleft[2][8];  // chroma neighbours [comp][-1..7]
-  int cdcp[2][4];                   // chroma DC predictions per (comp, block)
+  Pix tile[17 * TS];            // luma: row 0 / col 0 = reconstructed neighbours
+  int16_t res[16][16];          // Intra4x4 residual per blkIdx (raster)
+  int e4[16];                   // Intra4x4 neighbour vector of the current block
+  int lv16dc[16];               // Intra16x16 DC after the inverse Hadamard + scaling (raster)
+  Pix ctop[2][9], cleft[2][8];  // chroma neighbours [comp][-1..7]
+  int cdcp[2][4];               // chroma DC predictions per (comp, block)
   int saved_x;
-  uint8_t saved_y[16];
-  uint8_t saved_c[2][8];
+  Pix saved_y[16];
+  Pix saved_c[2][8];
   // Intra8x8: residual (16x16 raster, before the final rounding), the row above the MB at
   // x = 16..23 (top-right of 8x8 block 1), and the filtered references of the current block
   int r8[256];
-  uint8_t tr8[8];
+  Pix tr8[8];
   int e8t[16], e8l[8], e8tl;
   int f8t[16], f8l[8], f8tl;
 };
 
-// Intra_8x8 sample (8.3.2.2.2 .. 8.3.2.2.10) from the filtered references ft / fl / ftl
-
-__device__ __forceinline__ void decode_intra_mb(const DecodeArgs& a, DecIntraShared& S, int slot, int mx, int my) {
+template <class D>
+__device__ __forceinline__ void decode_intra_mb(const DecodeArgs<D>& a, DecIntraShared<typename D::Pix>& S, int slot,
+                                                int mx, int my) {
+  using Pix = typename D::Pix;
   const Geom& g = a.g;
   const int lane = lane_id();
   const int gy = lane & 3;
@@ -426,17 +513,19 @@ __device__ __forceinline__ void decode_intra_mb(const DecodeArgs& a, DecIntraSha
   const size_t o = static_cast<size_t>(slot) * g.nmb() + my * g.wmb + mx;
   const MbHeader* H = a.hdr + o;
   const int kind = __builtin_amdgcn_readfirstlane(H->kind);
-  const int qp = __builtin_amdgcn_readfirstlane(H->qp);
-  const int qpc = h264::chroma_qp(qp, a.chroma_qp_offset);
+  const int qpy = __builtin_amdgcn_readfirstlane(static_cast<int>(H->qp));
+  const int maxv = a.maxv(), half = a.half();
+  const int qp = luma_qp(a, qpy);
+  const int qpc = chroma_qp(a, qpy, a.chroma_qp_offset);
   const int mode16 = __builtin_amdgcn_readfirstlane(H->i16_mode);
   const int cmode = __builtin_amdgcn_readfirstlane(H->chroma_mode);
   const uint32_t mask = __builtin_amdgcn_readfirstlane(a.mask[o]);
   const uint32_t off = __builtin_amdgcn_readfirstlane(a.off[o]);
-  uint8_t* recy = rec_plane(a, a.rec_y, slot, g.ysize());
+  Pix* recy = rec_plane(a, a.rec_y, slot, g.ysize());
   // neighbour MBs are available when inside the picture and in this MB's slice (the
   // parser's records carry the slice index in pad0; 6.4.8)
   const int sl = __builtin_amdgcn_readfirstlane(H->pad0);
-  const Scaling sc = scaling_of(a, slot);
+  const Scaling sc = scaling_of(a.wp, slot);
   // constrained_intra_pred_flag: inter neighbours are not available for intra prediction
   const bool cip = a.wp && (a.wp[static_cast<size_t>(slot) * kWpEntries + kWpFlags] & 1);
   auto same = [&](int dx, int dy) {
@@ -450,24 +539,24 @@ __device__ __forceinline__ void decode_intra_mb(const DecodeArgs& a, DecIntraSha
   if (my > 0 && mx < g.wmb - 1 && same(1, -1)) mbav |= h264::AV_TOPRIGHT;
 
   if (kind == h264::MBK_IPCM) {
-    // I_PCM: the samples ride in the level pool (24 chunks: luma raster, Cb, Cr)
+    // I_PCM: the bd-bit samples (7.3.5.3) ride in the level pool (24 chunks: luma raster, Cb, Cr)
     const int16_t* pcm = a.coef + static_cast<size_t>(off) * 16;
     {
       const int y = lane >> 2, x4 = (lane & 3) * 4;
-      uint32_t word = 0;
+      int p[4];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) word |= static_cast<uint32_t>(pcm[y * 16 + x4 + k] & 0xFF) << (8 * k);
-      *reinterpret_cast<uint32_t*>(recy + static_cast<size_t>(Y0 + y) * W + X0 + x4) = word;
-      if ((lane & 3) == 3) S.saved_y[y] = static_cast<uint8_t>(word >> 24);
+      for (int k = 0; k < 4; ++k) p[k] = pcm[y * 16 + x4 + k] & maxv;
+      D::store4(recy + static_cast<size_t>(Y0 + y) * W + X0 + x4, p);
+      if ((lane & 3) == 3) S.saved_y[y] = static_cast<Pix>(p[3]);
     }
     if (lane < 32) {
       const int comp = lane >> 4, y = (lane >> 1) & 7, x4 = (lane & 1) * 4;
-      uint32_t word = 0;
+      int p[4];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) word |= static_cast<uint32_t>(pcm[256 + comp * 64 + y * 8 + x4 + k] & 0xFF) << (8 * k);
-      uint8_t* recc = rec_plane(a, comp == 0 ? a.rec_u : a.rec_v, slot, g.csize());
-      *reinterpret_cast<uint32_t*>(recc + static_cast<size_t>(my * 8 + y) * cw + mx * 8 + x4) = word;
-      if (lane & 1) S.saved_c[comp][y] = static_cast<uint8_t>(word >> 24);
+      for (int k = 0; k < 4; ++k) p[k] = pcm[256 + comp * 64 + y * 8 + x4 + k] & maxv;
+      Pix* recc = rec_plane(a, comp == 0 ? a.rec_u : a.rec_v, slot, g.csize());
+      D::store4(recc + static_cast<size_t>(my * 8 + y) * cw + mx * 8 + x4, p);
+      if (lane & 1) S.saved_c[comp][y] = static_cast<Pix>(p[3]);
     }
     if (lane < 16) a.nz[o * 16 + blk_x(lane) + 4 * blk_y(lane)] = 1;
     if (lane == 0) S.saved_x = my * g.wmb + mx;  // raster index: rows differ
@@ -487,26 +576,26 @@ __device__ __forceinline__ void decode_intra_mb(const DecodeArgs& a, DecIntraSha
     S.tr8[lane - 24] = ok ? recy[static_cast<size_t>(Y0 - 1) * W + x] : 0;
   } else if (lane >= 32 && lane < 48) {  // tile col 0, rows 1..16
     const int r = lane - 32;
-    uint8_t v = 0;
+    Pix v = 0;
     if (mbav & h264::AV_LEFT) v = S.saved_x == my * g.wmb + mx - 1 ? S.saved_y[r] : recy[static_cast<size_t>(Y0 + r) * W + X0 - 1];
     S.tile[(r + 1) * TS] = v;
   }
   if (lane < 18) {
     const int c = lane / 9, i = lane % 9;
-    const uint8_t* rc = rec_plane(a, c == 0 ? a.rec_u : a.rec_v, slot, g.csize());
+    const Pix* rc = rec_plane(a, c == 0 ? a.rec_u : a.rec_v, slot, g.csize());
     const int x = mx * 8 - 1 + i;
     S.ctop[c][i] = (i == 0 ? (mbav & h264::AV_TOPLEFT) : (mbav & h264::AV_TOP)) ? rc[static_cast<size_t>(my * 8 - 1) * cw + x] : 0;
   } else if (lane >= 48) {
     const int c = (lane - 48) >> 3, i = (lane - 48) & 7;
-    const uint8_t* rc = rec_plane(a, c == 0 ? a.rec_u : a.rec_v, slot, g.csize());
-    uint8_t v = 0;
+    const Pix* rc = rec_plane(a, c == 0 ? a.rec_u : a.rec_v, slot, g.csize());
+    Pix v = 0;
     if (mbav & h264::AV_LEFT) v = S.saved_x == my * g.wmb + mx - 1 ? S.saved_c[c][i] : rc[static_cast<size_t>(my * 8 + i) * cw + mx * 8 - 1];
     S.cleft[c][i] = v;
   }
   wave_sync();
   if (lane >= 16 && lane < 24) {
     const int c = (lane - 16) >> 2, b = (lane - 16) & 3;
-    S.cdcp[c][b] = h264::chroma_dc(S.ctop[c] + 1, S.cleft[c], mbav, b & 1, b >> 1);
+    S.cdcp[c][b] = h264::chroma_dc(S.ctop[c] + 1, S.cleft[c], mbav, b & 1, b >> 1, half);
   }
 
   // ---- luma
@@ -523,7 +612,7 @@ __device__ __forceinline__ void decode_intra_mb(const DecodeArgs& a, DecIntraSha
       for (int r = 0; r < 16; ++r)
         S.lv16dc[r] = qp >= 36 ? (d[r] * ls) << (qp / 6 - 6) : (d[r] * ls + (1 << (5 - qp / 6))) >> (6 - qp / 6);
     }
-    uint8_t top[16], left[16];
+    Pix top[16], left[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       top[i] = S.tile[1 + i];
@@ -531,7 +620,7 @@ __device__ __forceinline__ void decode_intra_mb(const DecodeArgs& a, DecIntraSha
     }
     int pa = 0, pb = 0, pc = 0;
     if (mode16 == 3) h264::i16_plane_params(top, left, static_cast<int>(S.tile[0]), &pa, &pb, &pc);
-    const int dc = mode16 == 2 ? h264::i16_dc(top, left, mbav) : 0;
+    const int dc = mode16 == 2 ? h264::i16_dc(top, left, mbav, half) : 0;
     int v[4], pr[4];
     dequant_row(a.coef, mask, off, blk, gy, qp, true, v, sc, 0);
     wave_sync();
@@ -543,13 +632,13 @@ __device__ __forceinline__ void decode_intra_mb(const DecodeArgs& a, DecIntraSha
     for (int x = 0; x < 4; ++x) {
       const int X = bx * 4 + x;
       const int p = mode16 == 0 ? static_cast<int>(S.tile[1 + X])
-                  : (mode16 == 1 ? lft : (mode16 == 2 ? dc : h264::clip1((pa + pb * (X - 7) + pc * (Yr - 7) + 16) >> 5)));
-      pr[x] = h264::clip1(p + v[x]);
+                  : (mode16 == 1 ? lft : (mode16 == 2 ? dc : h264::clip1((pa + pb * (X - 7) + pc * (Yr - 7) + 16) >> 5, maxv)));
+      pr[x] = h264::clip1(p + v[x], maxv);
     }
     wave_sync();
-    uint8_t* row = S.tile + (Yr + 1) * TS + bx * 4 + 1;
+    Pix* row = S.tile + (Yr + 1) * TS + bx * 4 + 1;
 #pragma unroll
-    for (int x = 0; x < 4; ++x) row[x] = static_cast<uint8_t>(pr[x]);
+    for (int x = 0; x < 4; ++x) row[x] = static_cast<Pix>(pr[x]);
   } else if (kind == h264::MBK_I8x8) {
     // Intra8x8: the four residual blocks at once (dequantise, 8x8 inverse transform), then
     // the four predictions in order from reference-filtered neighbours (8.3.2.2.1)
@@ -577,7 +666,7 @@ __device__ __forceinline__ void decode_intra_mb(const DecodeArgs& a, DecIntraSha
       const bool has_tl = b8 == 3 || (b8 == 0 ? (mbav & h264::AV_TOPLEFT) != 0
                                               : (b8 == 1 ? (mbav & h264::AV_TOP) != 0 : (mbav & h264::AV_LEFT) != 0));
       const bool has_tr = b8 == 2 || (b8 == 0 ? (mbav & h264::AV_TOP) != 0 : (b8 == 1 && (mbav & h264::AV_TOPRIGHT)));
-      const uint8_t* above = S.tile + by * TS + bx + 1;  // row above the block, x = 0
+      const Pix* above = S.tile + by * TS + bx + 1;  // row above the block, x = 0
       if (lane < 16) {
         int v = lane < 8 ? above[lane] : (has_tr ? (b8 == 1 ? S.tr8[lane - 8] : above[lane]) : above[7]);
         S.e8t[lane] = v;
@@ -615,7 +704,7 @@ __device__ __forceinline__ void decode_intra_mb(const DecodeArgs& a, DecIntraSha
       }
       wave_sync();
       const int mode = __builtin_amdgcn_readfirstlane(H->i4_modes[b8 * 4]);
-      int dc = 128;
+      int dc = half;
       if (mode == 2) {
         int st = 0, sl = 0;
 #pragma unroll
@@ -623,12 +712,12 @@ __device__ __forceinline__ void decode_intra_mb(const DecodeArgs& a, DecIntraSha
           st += has_top ? S.f8t[i] : 0;
           sl += has_left ? S.f8l[i] : 0;
         }
-        dc = (has_top && has_left) ? (st + sl + 8) >> 4 : (has_left ? (sl + 4) >> 3 : (has_top ? (st + 4) >> 3 : 128));
+        dc = (has_top && has_left) ? (st + sl + 8) >> 4 : (has_left ? (sl + 4) >> 3 : (has_top ? (st + 4) >> 3 : half));
       }
       const int x = lane & 7, y = lane >> 3;
       const int pr = i8_pred_sample(mode, x, y, S.f8t, S.f8l, S.f8tl, dc);
       const int rv = (S.r8[(by + y) * 16 + bx + x] + 32) >> 6;
-      S.tile[(by + 1 + y) * TS + bx + 1 + x] = static_cast<uint8_t>(h264::clip1(pr + rv));
+      S.tile[(by + 1 + y) * TS + bx + 1 + x] = static_cast<Pix>(h264::clip1(pr + rv, maxv));
       wave_sync();
     }
   } else {
@@ -645,7 +734,7 @@ __device__ __forceinline__ void decode_intra_mb(const DecodeArgs& a, DecIntraSha
       const int cbx = blk_x(b), cby = blk_y(b);
       const int av = i4_avail(b, mbav);
       if (lane < 13) {  // neighbour vector e[] of h264::i4_pred_sample, one entry per lane
-        const uint8_t* rowp = S.tile + (cby * 4) * TS + cbx * 4;
+        const Pix* rowp = S.tile + (cby * 4) * TS + cbx * 4;
         int v;
         if (lane == 0) v = rowp[0];
         else if (lane < 5) v = rowp[lane];
@@ -658,10 +747,10 @@ __device__ __forceinline__ void decode_intra_mb(const DecodeArgs& a, DecIntraSha
       if (lane < 4) {
         int pr[4];
 #pragma unroll
-        for (int x = 0; x < 4; ++x) pr[x] = h264::i4_pred_sample(mode, av, S.e4, x, gy);
-        uint8_t* row = S.tile + (cby * 4 + gy + 1) * TS + cbx * 4 + 1;
+        for (int x = 0; x < 4; ++x) pr[x] = h264::i4_pred_sample(mode, av, S.e4, x, gy, half);
+        Pix* row = S.tile + (cby * 4 + gy + 1) * TS + cbx * 4 + 1;
 #pragma unroll
-        for (int x = 0; x < 4; ++x) row[x] = static_cast<uint8_t>(h264::clip1(pr[x] + S.res[b][gy * 4 + x]));
+        for (int x = 0; x < 4; ++x) row[x] = static_cast<Pix>(h264::clip1(pr[x] + S.res[b][gy * 4 + x], maxv));
       }
       wave_sync();
     }
@@ -669,10 +758,10 @@ __device__ __forceinline__ void decode_intra_mb(const DecodeArgs& a, DecIntraSha
   wave_sync();
   {  // write the luma reconstruction
     const int y = lane >> 2, x4 = (lane & 3) * 4;
-    uint32_t word = 0;
+    int p[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) word |= static_cast<uint32_t>(S.tile[(y + 1) * TS + x4 + k + 1]) << (8 * k);
-    *reinterpret_cast<uint32_t*>(recy + static_cast<size_t>(Y0 + y) * W + X0 + x4) = word;
+    for (int k = 0; k < 4; ++k) p[k] = S.tile[(y + 1) * TS + x4 + k + 1];
+    D::store4(recy + static_cast<size_t>(Y0 + y) * W + X0 + x4, p);
   }
   if (lane < 16) a.nz[o * 16 + blk_x(lane) + 4 * blk_y(lane)] = (mask >> lane) & 1u;
 
@@ -692,14 +781,13 @@ __device__ __forceinline__ void decode_intra_mb(const DecodeArgs& a, DecIntraSha
       const int X = cbx + x;
       const int p = cmode == 0 ? S.cdcp[comp][cb]
                   : (cmode == 1 ? S.cleft[comp][Yc]
-                  : (cmode == 2 ? S.ctop[comp][1 + X] : h264::clip1((pa + pb * (X - 3) + pc * (Yc - 3) + 16) >> 5)));
-      pr[x] = h264::clip1(p + v[x]);
+                  : (cmode == 2 ? S.ctop[comp][1 + X] : h264::clip1((pa + pb * (X - 3) + pc * (Yc - 3) + 16) >> 5, maxv)));
+      pr[x] = h264::clip1(p + v[x], maxv);
     }
-    const uint32_t word = pack4(pr);
     if (lane < 32) {
-      uint8_t* recc = rec_plane(a, comp == 0 ? a.rec_u : a.rec_v, slot, g.csize());
-      *reinterpret_cast<uint32_t*>(recc + static_cast<size_t>(my * 8 + Yc) * cw + mx * 8 + cbx) = word;
-      if (cb & 1) S.saved_c[comp][(cb >> 1) * 4 + gy] = static_cast<uint8_t>(word >> 24);
+      Pix* recc = rec_plane(a, comp == 0 ? a.rec_u : a.rec_v, slot, g.csize());
+      D::store4(recc + static_cast<size_t>(my * 8 + Yc) * cw + mx * 8 + cbx, pr);
+      if (cb & 1) S.saved_c[comp][(cb >> 1) * 4 + gy] = static_cast<Pix>(pr[3]);
     }
   }
   if (lane < 16) S.saved_y[lane] = S.tile[(lane + 1) * TS + 16];
@@ -707,8 +795,9 @@ __device__ __forceinline__ void decode_intra_mb(const DecodeArgs& a, DecIntraSha
   wave_sync();
 }
 
-__global__ __launch_bounds__(64 * kDecIntraWaves) void decode_intra_wavefront(DecodeArgs a) {
-  __shared__ DecIntraShared SS[kDecIntraWaves];
+template <class D>
+__device__ __forceinline__ void decode_intra_rows(const DecodeArgs<D>& a) {
+  __shared__ DecIntraShared<typename D::Pix> SS[kDecIntraWaves];
   __shared__ int prog[kMaxRows];
   const Geom& g = a.g;
   const int slot = blockIdx.x;
@@ -719,7 +808,7 @@ __global__ __launch_bounds__(64 * kDecIntraWaves) void decode_intra_wavefront(De
   const int lane = lane_id();
   if (lane == 0) SS[w].saved_x = -2;
   __syncthreads();
-  DecIntraShared& S = SS[w];
+  DecIntraShared<typename D::Pix>& S = SS[w];
   for (int y = w; y < g.hmb; y += kDecIntraWaves) {
     if (run == 1) {  // I picture: every MB
       for (int x = 0; x < g.wmb; ++x) {
@@ -747,19 +836,34 @@ __global__ __launch_bounds__(64 * kDecIntraWaves) void decode_intra_wavefront(De
   }
 }
 
+__global__ __launch_bounds__(64 * kDecIntraWaves) void decode_intra_wavefront(DecodeArgs<Depth8> a) {
+  decode_intra_rows(a);
+}
+__global__ __launch_bounds__(64 * kDecIntraWaves) void decode_intra_wavefront16(DecodeArgs<DepthHi> a) {
+  decode_intra_rows(a);
+}
+
 }  // namespace gpu
 }  // namespace mivc
 
 using namespace mivc::gpu;
 
-static DecodeArgs make_decode_args(int B, int wmb, int hmb, uint8_t* rec_y, uint8_t* rec_u, uint8_t* rec_v,
-                                   const void* hdr, const uint32_t* mask, const uint32_t* off, const int16_t* coef,
-                                   const int8_t* run, int chroma_qp_offset, uint8_t* nz, int* err) {
-  DecodeArgs a;
+// One picture of every slot in the DPB layout: dpb_* = [B][dpb_n] picture buffers; the
+// decoded picture goes to buffer cur_idx[slot]; P and B macroblocks from reftab + the headers'
+// motion (and the side pool `sub` for MBF_SUB4 macroblocks).
+template <class D>
+static void launch_decode_picture(D depth, void (*inter)(DecodeArgs<D>), void (*intra)(DecodeArgs<D>), int B, int wmb,
+                                  int hmb, int dpb_n, typename D::Pix* dpb_y, typename D::Pix* dpb_u,
+                                  typename D::Pix* dpb_v, const int16_t* cur_idx, const int16_t* reftab,
+                                  const int16_t* wp, const int16_t* sub, const void* hdr, const uint32_t* mask,
+                                  const uint32_t* off, const int16_t* coef, const int8_t* run, int any_inter,
+                                  int chroma_qp_offset, uint8_t* nz, int* err, void* stream) {
+  DecodeArgs<D> a;
+  static_cast<D&>(a) = depth;
   a.g = Geom{B, wmb, hmb, wmb * 16, hmb * 16};
-  a.rec_y = rec_y;
-  a.rec_u = rec_u;
-  a.rec_v = rec_v;
+  a.rec_y = dpb_y;
+  a.rec_u = dpb_u;
+  a.rec_v = dpb_v;
   a.hdr = static_cast<const MbHeader*>(hdr);
   a.mask = mask;
   a.off = off;
@@ -768,31 +872,35 @@ static DecodeArgs make_decode_args(int B, int wmb, int hmb, uint8_t* rec_y, uint
   a.chroma_qp_offset = chroma_qp_offset;
   a.nz = nz;
   a.err = err;
-  a.dpb_n = 0;
-  a.cur_idx = nullptr;
-  a.reftab = nullptr;
-  a.wp = nullptr;
-  a.sub = nullptr;
-  return a;
-}
-
-// One picture of every slot in the DPB layout: rec_* = [B][dpb_n] picture buffers; the
-// decoded picture goes to buffer cur_idx[slot]; P and B macroblocks from reftab + the headers'
-// motion (and the side pool `sub` for MBF_SUB4 macroblocks).
-extern "C" void mivc_launch_decode_picture_dpb(int B, int wmb, int hmb, int dpb_n, uint8_t* dpb_y, uint8_t* dpb_u,
-                                               uint8_t* dpb_v, const int16_t* cur_idx, const int16_t* reftab,
-                                               const int16_t* wp, const int16_t* sub,
-                                               const void* hdr, const uint32_t* mask, const uint32_t* off,
-                                               const int16_t* coef, const int8_t* run, int any_inter,
-                                               int chroma_qp_offset, uint8_t* nz, int* err, void* stream) {
-  DecodeArgs a = make_decode_args(B, wmb, hmb, dpb_y, dpb_u, dpb_v, hdr, mask, off, coef, run,
-                                  chroma_qp_offset, nz, err);
   a.dpb_n = dpb_n;
   a.cur_idx = cur_idx;
   a.reftab = reftab;
   a.wp = wp;
   a.sub = sub;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (any_inter) hipLaunchKernelGGL(decode_inter_dpb, dim3(wmb * hmb, B), dim3(64), 0, s, a);
-  hipLaunchKernelGGL(decode_intra_wavefront, dim3(B), dim3(64 * kDecIntraWaves), 0, s, a);
+  if (any_inter) hipLaunchKernelGGL(inter, dim3(wmb * hmb, B), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(intra, dim3(B), dim3(64 * kDecIntraWaves), 0, s, a);
+}
+
+extern "C" void mivc_launch_decode_picture_dpb(int B, int wmb, int hmb, int dpb_n, uint8_t* dpb_y, uint8_t* dpb_u,
+                                               uint8_t* dpb_v, const int16_t* cur_idx, const int16_t* reftab,
+                                               const int16_t* wp, const int16_t* sub,
+                                               const void* hdr, const uint32_t* mask, const uint32_t* off,
+                                               const int16_t* coef, const int8_t* run, int any_inter,
+                                               int chroma_qp_offset, uint8_t* nz, int* err, void* stream) {
+  launch_decode_picture(Depth8{}, decode_inter_dpb, decode_intra_wavefront, B, wmb, hmb, dpb_n, dpb_y, dpb_u, dpb_v,
+                        cur_idx, reftab, wp, sub, hdr, mask, off, coef, run, any_inter, chroma_qp_offset, nz, err,
+                        stream);
+}
+
+// The same on planes of bd-bit samples (bd 9 or 10) in uint16_t.
+extern "C" void mivc_launch_decode_picture_dpb16(int B, int wmb, int hmb, int dpb_n, uint16_t* dpb_y, uint16_t* dpb_u,
+                                                 uint16_t* dpb_v, const int16_t* cur_idx, const int16_t* reftab,
+                                                 const int16_t* wp, const int16_t* sub,
+                                                 const void* hdr, const uint32_t* mask, const uint32_t* off,
+                                                 const int16_t* coef, const int8_t* run, int any_inter,
+                                                 int chroma_qp_offset, int bd, uint8_t* nz, int* err, void* stream) {
+  launch_decode_picture(DepthHi{bd}, decode_inter_dpb16, decode_intra_wavefront16, B, wmb, hmb, dpb_n, dpb_y, dpb_u,
+                        dpb_v, cur_idx, reftab, wp, sub, hdr, mask, off, coef, run, any_inter, chroma_qp_offset, nz,
+                        err, stream);
 }

@@ -27,8 +27,8 @@ result is identical either way (the CPU decoder is the bit-exact oracle of
 ``tests/test_gpu_decode.py``).
 
 High 10: ``GpuH264Decoder(high_depth="gpu")`` reconstructs 9- and 10-bit segments (BitDepthY ==
-BitDepthC) on the GPU too -- ``decode16.hip`` / ``deblock16.hip``, the same records on int16
-planes, in groups of their own beside the 8-bit ones (``tests/test_gpu_decode_high10.py``).
+BitDepthC) on the GPU too -- ``decode.hip``'s 16-bit instantiation (one kernel source for both
+depths) and ``deblock16.hip``, the same records on int16 planes, in groups of their own beside the 8-bit ones (``tests/test_gpu_decode_high10.py``).
 The option is opt-in until the path has been measured against the CPU decoder
 (``profiles/high10_gpu_decode.md``); the default ``"cpu"`` keeps such segments, and 11- to
 14-bit ones always, on the CPU decoder.
@@ -75,7 +75,8 @@ _META = ("pic_id", "ref_id", "nal_ref", "idr", "slice_type", "slice_qp", "alpha"
 M = {k: i for i, k in enumerate(_META)}
 
 
-# deblock16.hip and decode16.hip keep row progress counters for this many MB rows (kMaxRows)
+# deblock16.hip and decode.hip's intra wavefront (either depth) keep row progress counters for
+# this many MB rows (kMaxRows)
 _MAX_MB_ROWS_16 = 272
 
 

@@ -1,5 +1,5 @@
-"""GPU reconstruction of High 10 H.264 segments (decode16.hip + deblock16.hip, 9- and 10-bit
-samples in int16 planes) against the CPU decoder, bit-exact.
+"""GPU reconstruction of High 10 H.264 segments (decode.hip's 16-bit instantiation +
+deblock16.hip, 9- and 10-bit samples in int16 planes) against the CPU decoder, bit-exact.
 
 Every case decodes with ``GpuH264Decoder(high_depth="gpu")`` and compares every plane of every
 picture with ``host.decode``.  The 8-bit twin of each random stream is ``gpu_ok`` on every
@@ -98,17 +98,23 @@ def test_gpu_decode_high10_random_records(host, dec, name):
         assert top == want_top
 
 
-@pytest.mark.parametrize("name", ["tall_35_mb_rows", "wide_66_mb_columns"])
-def test_gpu_decode_8bit_twins_of_tall_and_wide(host, name):
-    """Control (passes without the 16-bit kernels): the 8-bit twins on the default decoder --
-    more MB rows than twice the waves of either wavefront workgroup, and a row longer than one
-    64-lane ballot of the P-picture intra scan."""
+@pytest.mark.parametrize("name", list(_CASES))
+def test_gpu_decode_8bit_twins_of_random_records(host, name):
+    """The 8-bit twin of every case on the default decoder: both depths are instantiations of
+    one kernel source, so each case guards the other depth's too.  Where the High 10 stream
+    reaches its depth's maximum, the twin reaches 255.  The tall and the wide case have more MB
+    rows than twice the waves of either wavefront workgroup, and a row longer than one 64-lane
+    ballot of the P-picture intra scan."""
     from govideocompressor_amd.models.h264_decode_gpu import GpuH264Decoder
     d8 = GpuH264Decoder()
     s = _stream(host, name, bit_depth=8)
     out = d8.decode([s])
-    assert out[0].path == "gpu" and out[0].bit_depth == 8 and out[0].y.dtype == torch.uint8
-    _compare(host, s, out[0])
+    assert d8.stats["segments_cpu"] == 0
+    assert out[0].path == "gpu" and out[0].bit_depth == 8
+    assert out[0].y.dtype == torch.uint8 and out[0].u.dtype == torch.uint8 and out[0].v.dtype == torch.uint8
+    top = _compare(host, s, out[0])
+    if _CASES[name][6] is not None:
+        assert top == 255
 
 
 class _Depth:
