@@ -113,9 +113,11 @@ void mivc_launch_encode_intra(int B, int wmb, int hmb, const uint8_t* src_y, con
                               const uint8_t* intra_flag, const int* intra_count, int* err, int use_i4x4,
                               const int8_t* aq, void* stream, int use_i8x8, const void* route, int nbuf,
                               int slice_rows, int trellis, float trellis_lambda, int* gprog, long long gprog_ints);
-void mivc_launch_deblock(int B, int wmb, int hmb, uint8_t* rec_y, uint8_t* rec_u, uint8_t* rec_v, const void* hdr,
-                         const uint8_t* nz, int chroma_qp_offset, int alpha_off, int beta_off, int* err,
+void mivc_launch_deblock(int B, int wmb, int hmb, uint8_t* rec_y, uint8_t* rec_u, uint8_t* rec_v, const uint8_t* bs,
+                         const uint32_t* info, int chroma_qp_offset, int alpha_off, int beta_off, int* err,
                          void* stream, const void* route, int nbuf);
+void mivc_launch_deblock_bs(int B, int wmb, int hmb, const void* hdr, const uint8_t* nz, uint8_t* bs, uint32_t* info,
+                            void* stream, const void* route);
 void mivc_launch_decode_picture_dpb(int B, int wmb, int hmb, int dpb_n, uint8_t* dpb_y, uint8_t* dpb_u, uint8_t* dpb_v,
                                     const int16_t* cur_idx, const int16_t* reftab, const int16_t* wp, const int16_t* sub,
                                     const void* hdr, const uint32_t* mask, const uint32_t* off,
@@ -543,13 +545,28 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("intra_flag"), py::arg("intra_count"), py::arg("err"), py::arg("use_i4x4"), py::arg("stream"),
      py::arg("aq") = 0, py::arg("use_i8x8") = 0, py::arg("route") = 0, py::arg("nbuf") = 0, py::arg("slice_rows") = 0,
      py::arg("trellis") = 0, py::arg("trellis_lambda") = 1.0f, py::arg("gprog") = 0, py::arg("gprog_ints") = 0);
+  // bs / info: the buffers deblock_bs filled for these records (hdr, nz) on this stream
   m.def("deblock", [](int B, int wmb, int hmb, uintptr_t ry, uintptr_t ru, uintptr_t rv, uintptr_t hdr, uintptr_t nz,
-                      int cqo, int alpha_off, int beta_off, uintptr_t err, uintptr_t stream, uintptr_t route, int nbuf) {
-    mivc_launch_deblock(B, wmb, hmb, P<uint8_t>(ry), P<uint8_t>(ru), P<uint8_t>(rv), P<void>(hdr), P<uint8_t>(nz),
+                      int cqo, int alpha_off, int beta_off, uintptr_t err, uintptr_t stream, uintptr_t route, int nbuf,
+                      uintptr_t bs, uintptr_t info) {
+    if (wmb < 1 || wmb > 480 || hmb < 1 || hmb > 272) throw std::invalid_argument("deblock: at most 480 x 272 MBs");
+    if (!bs || !info) throw std::invalid_argument("deblock: needs the bs and info buffers of deblock_bs");
+    (void)hdr;
+    (void)nz;
+    mivc_launch_deblock(B, wmb, hmb, P<uint8_t>(ry), P<uint8_t>(ru), P<uint8_t>(rv), P<uint8_t>(bs), P<uint32_t>(info),
                         cqo, alpha_off, beta_off, P<int>(err), S(stream), P<void>(route), nbuf);
   }, py::arg("B"), py::arg("wmb"), py::arg("hmb"), py::arg("ry"), py::arg("ru"), py::arg("rv"), py::arg("hdr"),
      py::arg("nz"), py::arg("cqo"), py::arg("alpha_off"), py::arg("beta_off"), py::arg("err"), py::arg("stream"),
-     py::arg("route") = 0, py::arg("nbuf") = 0);
+     py::arg("route") = 0, py::arg("nbuf") = 0, py::arg("bs") = 0, py::arg("info") = 0);
+  // boundary strengths [B, nmb, 16] (4 bits per segment, the parser's layout) and info words
+  // [B, nmb] (QP, one "on" bit per direction and edge) of the records, for deblock
+  m.def("deblock_bs", [](int B, int wmb, int hmb, uintptr_t hdr, uintptr_t nz, uintptr_t bs, uintptr_t info,
+                         uintptr_t stream, uintptr_t route) {
+    if (!hdr || !nz || !bs || !info) throw std::invalid_argument("deblock_bs: needs hdr, nz, bs and info");
+    mivc_launch_deblock_bs(B, wmb, hmb, P<void>(hdr), P<uint8_t>(nz), P<uint8_t>(bs), P<uint32_t>(info), S(stream),
+                           P<void>(route));
+  }, py::arg("B"), py::arg("wmb"), py::arg("hmb"), py::arg("hdr"), py::arg("nz"), py::arg("bs"), py::arg("info"),
+     py::arg("stream"), py::arg("route") = 0);
   m.def("decode_picture_dpb", [](int B, int wmb, int hmb, int dpb_n, uintptr_t y, uintptr_t u, uintptr_t v,
                                  uintptr_t cur_idx, uintptr_t reftab, uintptr_t wp, uintptr_t sub,
                                  uintptr_t hdr, uintptr_t mask, uintptr_t off, uintptr_t coef, uintptr_t run,

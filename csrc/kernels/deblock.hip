@@ -9,7 +9,8 @@
 // MB the 16 lines of an edge are filtered in parallel (lanes 0-15 luma, 16-31
 // chroma), edges in the normative order (vertical left->right, then horizontal
 // top->bottom).  Boundary strengths are derived per MB from the decision
-// records (intra, non-zero coefficients, motion vectors).
+// records (intra, non-zero coefficients, motion vectors) by a parallel pre-pass,
+// deblock_bs; the wavefront skips what they switch off.
 #include "kcommon.h"
 
 namespace mivc {
@@ -20,21 +21,42 @@ using h264::MbHeader;
 struct DeblockArgs {
   Geom g;
   uint8_t *rec_y, *rec_u, *rec_v;
-  const MbHeader* hdr;
-  const uint8_t* nz;   // [B, nmb, 16] raster
   int chroma_qp_offset;
   int alpha_off, beta_off;  // slice_alpha_c0_offset_div2*2, slice_beta_offset_div2*2
   int* err;
-  // decoder use: boundary strengths computed by the parser ([B, nmb, 32], dir * 16 +
-  // edge * 4 + segment; null: derive from the records) and the DPB layout of the planes
-  // (rec_* = [B][dpb_n] pictures, filtering picture cur_idx[slot]; dpb_n 0: [B] pictures)
+  // boundary strengths [B, nmb, 16] and info words [B, nmb] (layout below): the encoder's
+  // come from deblock_bs; the decoder's strengths come from the parser, and with info null
+  // the wavefront takes the QPs from hdr and forms the info word's "on" bits from the
+  // strengths itself.  DPB layout of the decoder's planes: rec_* = [B][dpb_n] pictures,
+  // filtering picture cur_idx[slot]; dpb_n 0: [B] pictures
   const uint8_t* bs_in;
+  const uint32_t* info;
+  const MbHeader* hdr;
   int dpb_n;
   const int16_t* cur_idx;
   // encoder routing (route.h): rec_* are pools [B, nbuf, plane]; slots whose picture is not
   // flagged SF_DEBLOCK are left alone
   const SlotRoute* rt;
   int nbuf;
+};
+
+// Per-MB input of the wavefront, written by deblock_bs:
+//   bs   16 bytes, the parser's layout (h264_decoder.h DecodedPicture::bs): segment
+//        i = dir * 16 + edge * 4 + k (dir 0: vertical edges, k: 4-sample segment along the
+//        edge), 4 bits each in byte i / 2, low nibble for even i.  MB edges on the picture
+//        border and the odd inner edges of MBF_T8x8 MBs are 0.
+//   info one word: bits 0..7 the MB's QP; bit kInfoOnShift + dir * 4 + edge set when some
+//        segment of that edge has bS > 0 (so bits 8..15 == 0: the MB filters nothing)
+constexpr int kInfoOnShift = 8;
+
+// deblock_bs: the records (hdr, nz) -> bs, info
+struct DeblockBsArgs {
+  Geom g;
+  const MbHeader* hdr;
+  const uint8_t* nz;  // [B, nmb, 16] raster
+  uint8_t* bs;
+  uint32_t* info;
+  const SlotRoute* rt;
 };
 
 constexpr int kDeblockWaves = 16;
@@ -54,17 +76,15 @@ constexpr int kMaxCols = 480;   // MB columns (8K: 7680 / 16)
 // The wavefront hands data on through LDS only: a row reads its top halo (the bottom 4
 // luma / 2 chroma rows of the MB above, as they are after that MB's right neighbour ran)
 // from the producer's ring, never from global memory, so no global store is waited on.
-// Unfiltered inputs (reconstruction, decision records) are prefetched one MB ahead.
-// Every output dword is stored exactly once, by the step after which it is final:
+// Unfiltered inputs (reconstruction, strengths, info words) are prefetched one MB ahead.
+// Every output dword is stored at most once (not at all when no edge that reaches it is on:
+// the filter works in place), by the step after which it is final:
 //   luma cols 0..11 rows 0..12 -> own step; cols 12..15 rows 0..12 -> right neighbour's
 //   step; rows 13..15 -> the step of the MB below (from its top halo); last row / column:
 //   own step (chroma alike with cols 0..3 / 4..7 and rows 0..6 / 7).
 struct DeblockShared {
   alignas(16) uint8_t ty[LT * LT];
   alignas(16) uint8_t tc[2][CT * CT];
-  alignas(16) uint32_t hdrw[3][12];  // first 48 B of the MbHeader of the current, left and top MB
-  uint32_t nzw[3][4];                // their non-zero flags (16 bytes each)
-  int bs[2][4][4];                   // [dir][edge][segment]
   int par[2][2][2][5];               // [dir][mb edge / inner][luma / chroma]: alpha, beta, tc0 for bS 1..3
   uint32_t left_y[16];               // previous MB's cols 12..15 (final but for rows 13..15)
   uint32_t left_c[2][8];             // previous MB's chroma cols 4..7
@@ -117,17 +137,89 @@ __device__ __forceinline__ void filt(uint32_t& P, uint32_t& Q, int bs, int alpha
 // The four edges of one direction on lane-local lines: d[0..4] = 4-sample groups across
 // the line (luma: halo, 0..3, 4..7, 8..11, 12..15; chroma: halo, 0..3, 0..3, 4..7 -- the
 // chroma edges 0 and 4 run as edges 0 and 2, which touch disjoint samples of the copy).
-__device__ __forceinline__ void edges4(uint32_t (&d)[5], const DeblockShared& S, int dir, int line, bool chroma,
-                                       bool has_nb) {
+// bw0 / bw1: the MB's strengths of this direction (edges 0, 1 / 2, 3: eight nibbles each).
+// on: wave-uniform, bit e set when some lane of the wave has edge e on; the others are not run.
+__device__ __forceinline__ void edges4(uint32_t (&d)[5], const DeblockShared& S, uint32_t bw0, uint32_t bw1,
+                                       uint32_t on, int dir, int line, bool chroma, bool has_nb) {
   const int seg = chroma ? (line >> 1) : (line >> 2);
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    int bs = S.bs[dir][e][seg & 3];
+    if (!(on & (1u << e))) continue;
+    int bs = ((e < 2 ? bw0 : bw1) >> (((e & 1) * 4 + (seg & 3)) * 4)) & 15;
     if (e == 0 && !has_nb) bs = 0;
     if (chroma && (e & 1)) bs = 0;
     const int* P = S.par[dir][e == 0 ? 0 : 1][chroma ? 1 : 0];
     const int tc0 = P[2 + (bs > 0 && bs < 4 ? bs - 1 : 0)];
     filt(d[e], d[e + 1], bs, P[0], P[1], tc0, chroma);
+  }
+}
+
+// Boundary strengths and info words of every MB, ahead of the wavefront: nothing here depends
+// on filtered samples.  Eight lanes per MB, lane = dir * 4 + edge, each the four segments of
+// its edge (two bytes of the MB's 16).
+constexpr int kBsThreads = 256;
+__global__ __launch_bounds__(kBsThreads) void deblock_bs(DeblockBsArgs a) {
+  const Geom& g = a.g;
+  const int slot = blockIdx.y;
+  if (a.rt && (a.rt[slot].kind < 0 || !(a.rt[slot].flags & SF_DEBLOCK))) return;  // uniform per workgroup
+  const int nmb = g.nmb(), wmb = g.wmb;
+  const int mb = blockIdx.x * (kBsThreads / 8) + (threadIdx.x >> 3);
+  const int t = threadIdx.x & 7, dir = t >> 2, e = t & 3;
+  const bool ok = mb < nmb;
+  const size_t smb = static_cast<size_t>(slot) * nmb + (ok ? mb : 0);
+  const MbHeader* HQ = a.hdr + smb;
+  uint32_t segs = 0;  // four nibbles, segment k in bits 4k..4k+3
+  if (ok) {
+    const int x = mb % wmb, y = mb / wmb;
+    const bool mbedge = e == 0;
+    const bool has_nb = !mbedge || (dir == 0 ? x > 0 : y > 0);
+    if (has_nb) {
+      const size_t sp = mbedge ? (dir == 0 ? smb - 1 : smb - wmb) : smb;
+      const MbHeader* HP = a.hdr + sp;
+      const uint8_t* nzbp = a.nz + sp * 16;
+      const uint8_t* nzb0 = a.nz + smb * 16;
+      const bool iq = h264::mbk_is_intra(HQ->kind), ip = h264::mbk_is_intra(HP->kind);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int rq = dir == 0 ? (e + 4 * k) : (k + 4 * e);
+        const int rp = dir == 0 ? (mbedge ? 3 + 4 * k : e - 1 + 4 * k) : (mbedge ? k + 12 : k + 4 * (e - 1));
+        int bs;
+        if ((e & 1) && (HQ->flags & h264::MBF_T8x8)) bs = 0;  // 8x8 transform: no 4-sample inner edges
+        else if (mbedge && (iq || ip)) bs = 4;
+        else if (iq || ip) bs = 3;
+        else if (nzbp[rp] || nzb0[rq]) bs = 2;
+        else {
+          // bS 1: different reference pictures / number of vectors, or a vector component
+          // differing by >= 4 quarter samples (clause 8.7.2.1).  Reference identity is
+          // (list, ref_idx): the encoder's lists hold disjoint pictures (past anchors in
+          // list 0, the future anchor in list 1), and the GPU decode path brings the
+          // parser's strengths.
+          const int qp_ = ((rp >> 3) & 1) * 2 + ((rp & 3) >> 1), qq_ = ((rq >> 3) & 1) * 2 + ((rq & 3) >> 1);
+          bool diff = false;
+#pragma unroll
+          for (int l = 0; l < 2; ++l) {
+            const int fp = HP->ref[l][qp_], fq = HQ->ref[l][qq_];
+            if ((fp >= 0) != (fq >= 0) || (fp >= 0 && fp != fq)) {
+              diff = true;
+            } else if (fp >= 0) {
+              const int dx = HP->mv[l][qp_][0] - HQ->mv[l][qq_][0], dy = HP->mv[l][qp_][1] - HQ->mv[l][qq_][1];
+              diff |= dx >= 4 || dx <= -4 || dy >= 4 || dy <= -4;
+            }
+          }
+          bs = diff ? 1 : 0;
+        }
+        segs |= static_cast<uint32_t>(bs) << (4 * k);
+      }
+    }
+  }
+  // the MB's eight "edge on" bits, from its eight lanes
+  const unsigned long long on = __ballot(segs != 0);
+  if (ok) {
+    *reinterpret_cast<uint16_t*>(a.bs + smb * 16 + t * 2) = static_cast<uint16_t>(segs);
+    if (t == 0) {
+      const uint32_t bits = static_cast<uint32_t>(on >> (lane_id() & 56)) & 255u;
+      a.info[smb] = static_cast<uint32_t>(HQ->qp & 255) | (bits << kInfoOnShift);
+    }
   }
 }
 
@@ -155,7 +247,7 @@ __global__ __launch_bounds__(64 * kDeblockWaves) void deblock_wavefront(DeblockA
     T.cqp[i] = h264::kChromaQp[i];
   }
   __syncthreads();
-  const int w = wave_id();
+  const int w = __builtin_amdgcn_readfirstlane(wave_id());  // the skip tests below are scalar
   // lane-derived values are recomputed per step from an opaque lane id instead of being
   // hoisted out of the loops (at 16 waves the hoisted addresses spilled to scratch)
   auto opaque_lane = []() { int l = lane_id(); asm volatile("" : "+v"(l)); return l; };
@@ -172,16 +264,18 @@ __global__ __launch_bounds__(64 * kDeblockWaves) void deblock_wavefront(DeblockA
   uint8_t* recy = a.rec_y + pic * g.ysize();
   uint8_t* const rcu = a.rec_u + pic * g.csize();
   uint8_t* const rcv = a.rec_v + pic * g.csize();
-  const uint8_t* bs_in = a.bs_in ? a.bs_in + static_cast<size_t>(slot) * g.nmb() * 16 : nullptr;
   auto recc = [&](int c) { return c ? rcv : rcu; };
-  const uint32_t* hdr32 = reinterpret_cast<const uint32_t*>(a.hdr) + static_cast<size_t>(slot) * g.nmb() * 16;
-  const uint32_t* nz32 = reinterpret_cast<const uint32_t*>(a.nz) + static_cast<size_t>(slot) * g.nmb() * 4;
+  const uint32_t* bs32 = reinterpret_cast<const uint32_t*>(a.bs_in) + static_cast<size_t>(slot) * g.nmb() * 4;
+  // info words, or (decoder) word 0 of each 16-word MbHeader: kind, cbp, qp, i16_mode
+  const bool has_info = a.info != nullptr;
+  const uint32_t* info32 = has_info ? a.info + static_cast<size_t>(slot) * g.nmb()
+                                    : reinterpret_cast<const uint32_t*>(a.hdr) + static_cast<size_t>(slot) * g.nmb() * 16;
+  const int info_step = has_info ? 1 : 16, qp_shift = has_info ? 0 : 16;
 
   // unfiltered inputs of MB (x, y), branch-free (three loads per lane, lane-selected
   // addresses) so that they stay in flight across the previous MB's filtering:
-  //   luma lanes: their row (2 x 8 bytes); chroma lanes: their row (8 bytes); and every
-  //   lane one record word: 0..11 current header, 12..23 top header, 24..27 current nz,
-  //   28..31 top nz
+  //   luma lanes: their row (2 x 8 bytes); chroma lanes: their row (8 bytes); and lanes
+  //   0..3 the MB's four strength words, lane 4 its info word, lane 5 the top MB's
   auto load_inputs = [&](int x, int y, uint32_t (&v)[5]) {
     DB_LANE_VALUES
     (void)line;
@@ -190,9 +284,8 @@ __global__ __launch_bounds__(64 * kDeblockWaves) void deblock_wavefront(DeblockA
     if (is_c) a1 = a2 = recc(ccomp) + static_cast<size_t>(y * 8 + cline) * cw + x * 8;
     const size_t mb = static_cast<size_t>(y) * wmb + x;
     const size_t mbt = y > 0 ? mb - wmb : mb;
-    const uint32_t* a3 = hl < 12 ? hdr32 + mb * 16 + hl
-                                 : (hl < 24 ? hdr32 + mbt * 16 + (hl - 12)
-                                            : (hl < 28 ? nz32 + mb * 4 + (hl - 24) : nz32 + mbt * 4 + (hl - 28)));
+    const size_t mbtr = y > 0 && x + 1 < wmb ? mb - wmb + 1 : mb;  // lane 6: the top-right MB's info word
+    const uint32_t* a3 = hl < 4 ? bs32 + mb * 4 + hl : info32 + (hl == 5 ? mbt : (hl == 6 ? mbtr : mb)) * info_step;
     const uint2 q1 = *reinterpret_cast<const uint2*>(a1);
     const uint2 q2 = *reinterpret_cast<const uint2*>(a2);
     v[0] = q1.x; v[1] = q1.y; v[2] = q2.x; v[3] = q2.y;
@@ -213,6 +306,8 @@ __global__ __launch_bounds__(64 * kDeblockWaves) void deblock_wavefront(DeblockA
     if (half && w < kDeblockWaves - 1 && yl >= 2 * kDeblockWaves && row_ok && (lane_id() & 31) == 0)
       row_wait_lds(prog, yl - 2 * kDeblockWaves + 1, wmb, a.err);
     uint32_t nxt[5] = {0, 0, 0, 0, 0};
+    int left_qp = 0;          // QP of MB (x - 1, y)
+    bool left_quiet = false;  // MB (x - 1, y) had no edge on
     if (!half) load_inputs(0, y, nxt);
     for (int step = 0; step < wmb + 2; ++step) {
       const int x = half ? step - 2 : step;
@@ -220,61 +315,42 @@ __global__ __launch_bounds__(64 * kDeblockWaves) void deblock_wavefront(DeblockA
       DB_LANE_VALUES
       const uint32_t cur[5] = {nxt[0], nxt[1], nxt[2], nxt[3], nxt[4]};
       if (row_ok && x + 1 >= 0 && x + 1 < wmb) load_inputs(x + 1, y, nxt);
+      // ---- the two MBs' strengths and info words, from the lanes that loaded them.  The
+      // filter below is skipped per edge, per direction and per step in wave-uniform flow:
+      // `on` has bit dir * 4 + edge set when that edge is on in either MB of this step.
+      const int rec = static_cast<int>(cur[4]);
+      const bool act_u = yu < hmb && step < wmb, act_l = yl < hmb && step >= 2;
+      uint32_t on_u, on_l;
+      if (has_info) {
+        on_u = (static_cast<uint32_t>(__builtin_amdgcn_readlane(rec, 4)) >> kInfoOnShift) & 255u;
+        on_l = (static_cast<uint32_t>(__builtin_amdgcn_readlane(rec, 36)) >> kInfoOnShift) & 255u;
+      } else {
+        on_u = on_l = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {  // word i: edges 2 i and 2 i + 1 of direction i / 2
+          const uint32_t wu = static_cast<uint32_t>(__builtin_amdgcn_readlane(rec, i));
+          const uint32_t wl = static_cast<uint32_t>(__builtin_amdgcn_readlane(rec, 32 + i));
+          on_u |= ((wu & 0xFFFFu) ? 1u : 0u) << (2 * i) | ((wu >> 16) ? 2u : 0u) << (2 * i);
+          on_l |= ((wl & 0xFFFFu) ? 1u : 0u) << (2 * i) | ((wl >> 16) ? 2u : 0u) << (2 * i);
+        }
+      }
+      if (!act_u) on_u = 0;
+      if (!act_l) on_l = 0;
+      if (step == 0) on_u &= ~1u;   // no left neighbour
+      if (step == 2) on_l &= ~1u;
+      if (yu == 0) on_u &= ~16u;    // no top neighbour
+      const uint32_t on = on_u | on_l;
+#define DB_REC(i) static_cast<uint32_t>(half ? __builtin_amdgcn_readlane(rec, 32 + (i)) : __builtin_amdgcn_readlane(rec, (i)))
+      const uint32_t bsw[4] = {DB_REC(0), DB_REC(1), DB_REC(2), DB_REC(3)};
+      const uint32_t inf_q = DB_REC(4), inf_t = DB_REC(5), inf_tr = DB_REC(6);
+      const int qpq = (inf_q >> qp_shift) & 255u, qpt = (inf_t >> qp_shift) & 255u;
+#undef DB_REC
       if (act) {
         const bool has_left = x > 0, last_col = x == wmb - 1;
-        // ---- decision records -> LDS, boundary strengths, filter parameters
-        {
-          uint32_t* dst = hl < 12 ? &S.hdrw[0][hl]
-                                  : (hl < 24 ? &S.hdrw[2][hl - 12] : (hl < 28 ? &S.nzw[0][hl - 24] : &S.nzw[2][hl - 28]));
-          *dst = cur[4];
-        }
-        wave_sync();
-        const MbHeader* HQ = reinterpret_cast<const MbHeader*>(S.hdrw[0]);
-        {
-          const int dir = hl >> 4, e = (hl >> 2) & 3, k = hl & 3;
-          int bs = 0;
-          const bool mbedge = e == 0;
-          if (bs_in) {
-            // 4 bits per segment (h264_decoder.h DecodedPicture::bs)
-            bs = (bs_in[(static_cast<size_t>(y) * wmb + x) * 16 + (hl >> 1)] >> ((hl & 1) * 4)) & 15;
-          } else if (!mbedge || (dir == 0 ? has_left : has_top)) {
-            const int pw = mbedge ? (dir == 0 ? 1 : 2) : 0;
-            const MbHeader* HP = reinterpret_cast<const MbHeader*>(S.hdrw[pw]);
-            const uint8_t* nzbp = reinterpret_cast<const uint8_t*>(S.nzw[pw]);
-            const uint8_t* nzb0 = reinterpret_cast<const uint8_t*>(S.nzw[0]);
-            const int rq = dir == 0 ? (e + 4 * k) : (k + 4 * e);
-            const int rp = dir == 0 ? (mbedge ? 3 + 4 * k : e - 1 + 4 * k) : (mbedge ? k + 12 : k + 4 * (e - 1));
-            const bool iq = h264::mbk_is_intra(HQ->kind), ip = h264::mbk_is_intra(HP->kind);
-            if ((e & 1) && (HQ->flags & h264::MBF_T8x8)) bs = 0;  // 8x8 transform: no 4-sample inner edges
-            else if (mbedge && (iq || ip)) bs = 4;
-            else if (iq || ip) bs = 3;
-            else if (nzbp[rp] || nzb0[rq]) bs = 2;
-            else {
-              // bS 1: different reference pictures / number of vectors, or a vector component
-              // differing by >= 4 quarter samples (clause 8.7.2.1).  Reference identity is
-              // (list, ref_idx): the encoder's lists hold disjoint pictures (past anchors in
-              // list 0, the future anchor in list 1), and the GPU decode path takes P only.
-              const int qp_ = ((rp >> 3) & 1) * 2 + ((rp & 3) >> 1), qq_ = ((rq >> 3) & 1) * 2 + ((rq & 3) >> 1);
-              bool diff = false;
-#pragma unroll
-              for (int l = 0; l < 2; ++l) {
-                const int fp = HP->ref[l][qp_], fq = HQ->ref[l][qq_];
-                if ((fp >= 0) != (fq >= 0) || (fp >= 0 && fp != fq)) {
-                  diff = true;
-                } else if (fp >= 0) {
-                  const int dx = HP->mv[l][qp_][0] - HQ->mv[l][qq_][0], dy = HP->mv[l][qp_][1] - HQ->mv[l][qq_][1];
-                  diff |= dx >= 4 || dx <= -4 || dy >= 4 || dy <= -4;
-                }
-              }
-              bs = diff ? 1 : 0;
-            }
-          }
-          S.bs[dir][e][k] = bs;
-        }
-        if (hl < 8) {
+        // ---- filter parameters of the MB edges and the inner edges
+        if (on && hl < 8) {
           const int dir = hl >> 2, inner = (hl >> 1) & 1, ch = hl & 1;
-          const int qpq = HQ->qp;
-          const int qpn = reinterpret_cast<const MbHeader*>(S.hdrw[dir == 0 ? 1 : 2])->qp;
+          const int qpn = dir == 0 ? left_qp : qpt;
           int qq = qpq, qn = inner ? qpq : qpn;
           if (ch) {
             qq = T.cqp[clampi(qq + a.chroma_qp_offset, 0, 51)];
@@ -289,6 +365,7 @@ __global__ __launch_bounds__(64 * kDeblockWaves) void deblock_wavefront(DeblockA
           P[3] = T.tc0[ia][1];
           P[4] = T.tc0[ia][2];
         }
+        left_qp = qpq;
         // ---- top halo: upper half from the previous wave's lower ring (waits for
         // MB (x + 1, y - 1)), lower half from this wave's upper ring (written last step)
         if (has_top) {
@@ -314,7 +391,7 @@ __global__ __launch_bounds__(64 * kDeblockWaves) void deblock_wavefront(DeblockA
           d[0] = has_left ? S.left_c[ccomp][cline] : 0u;
           d[1] = cur[0]; d[2] = cur[0]; d[3] = cur[1]; d[4] = 0u;
         }
-        edges4(d, S, 0, line, is_c, has_left);
+        if (on & 15u) edges4(d, S, bsw[0], bsw[1], on & 15u, 0, line, is_c, has_left);
         if (!is_c) {
           uint32_t* row = reinterpret_cast<uint32_t*>(&S.ty[(hl + 4) * LT]);
           row[0] = d[0]; row[1] = d[1]; row[2] = d[2]; row[3] = d[3]; row[4] = d[4];
@@ -326,8 +403,9 @@ __global__ __launch_bounds__(64 * kDeblockWaves) void deblock_wavefront(DeblockA
         }
         wave_sync();
 
-        // ---- horizontal edges on columns gathered from the tile
-        {
+        // ---- horizontal edges on columns gathered from the tile (with none on in either
+        // MB the tile already holds what the stores and hand-offs below take)
+        if (on >> 4) {
           uint8_t* col = is_c ? &S.tc[ccomp][4 + cline] : &S.ty[4 + hl];
           const int pitch = is_c ? CT : LT;
           const int nw = is_c ? 3 : 5;
@@ -342,7 +420,7 @@ __global__ __launch_bounds__(64 * kDeblockWaves) void deblock_wavefront(DeblockA
             }
           }
           if (is_c) { c[4] = 0; c[3] = c[2]; c[2] = c[1]; }
-          edges4(c, S, 1, line, is_c, has_top);
+          edges4(c, S, bsw[2], bsw[3], on >> 4, 1, line, is_c, has_top);
           if (is_c) { c[1] = (c[1] & 0x00FFFFFFu) | (c[2] & 0xFF000000u); c[2] = c[3]; }
 #pragma unroll
           for (int k = 0; k < 5; ++k) {
@@ -354,30 +432,40 @@ __global__ __launch_bounds__(64 * kDeblockWaves) void deblock_wavefront(DeblockA
         }
         wave_sync();
 
-        // ---- global stores (each output word exactly once, see the layout note)
+        // ---- global stores (each output word exactly once, see the layout note).  The
+        // filter works in place, so words that no edge can have changed are not stored: the
+        // own part when this MB has no edge on; the left MB's last columns when it had none
+        // and this MB's left edge is off; the top MB's last rows when it had none, its right
+        // neighbour's left edge is off and this MB's top edge is off.
         {
+          const uint32_t own_on = half ? on_l : on_u;
+          const bool top_quiet = ((inf_t >> kInfoOnShift) & 255u) == 0;
+          const bool tr_left_on = y > 0 && !last_col && ((inf_tr >> kInfoOnShift) & 1u);
+          const bool st_own = !has_info || own_on != 0;
+          const bool st_left = !has_info || !left_quiet || (own_on & 1u);
+          const bool st_top = !has_info || !top_quiet || tr_left_on || (own_on & 16u);
           const int r = hl & 15;
           const bool rowok = r <= 12 || last_row;
           if (!is_c) {
-            if (rowok) {  // own cols 0..11
+            if (rowok && st_own) {  // own cols 0..11
               const uint8_t* t = &S.ty[(r + 4) * LT + 4];
               uint32_t* o = reinterpret_cast<uint32_t*>(recy + static_cast<size_t>(y * 16 + r) * W + x * 16);
               const uint32_t* ti = reinterpret_cast<const uint32_t*>(t);
               o[0] = ti[0]; o[1] = ti[1]; o[2] = ti[2];
               if (last_col) o[3] = ti[3];
             }
-          } else if (rowok && has_left) {  // left MB's cols 12..15
+          } else if (rowok && has_left && st_left) {  // left MB's cols 12..15
             *reinterpret_cast<uint32_t*>(recy + static_cast<size_t>(y * 16 + r) * W + x * 16 - 4) =
                 *reinterpret_cast<const uint32_t*>(&S.ty[(r + 4) * LT]);
           }
           if (hl < 3) {  // MB (x, y-1) rows 13..15 from the top halo
-            if (has_top) {
+            if (has_top && st_top) {
               const uint32_t* ti = reinterpret_cast<const uint32_t*>(&S.ty[(1 + hl) * LT + 4]);
               uint32_t* o = reinterpret_cast<uint32_t*>(recy + static_cast<size_t>(y * 16 - 3 + hl) * W + x * 16);
               o[0] = ti[0]; o[1] = ti[1]; o[2] = ti[2]; o[3] = ti[3];
             }
           } else if (hl < 5) {  // chroma MB (x, y-1) row 7
-            if (has_top) {
+            if (has_top && st_top) {
               const int c = hl - 3;
               const uint32_t* ti = reinterpret_cast<const uint32_t*>(&S.tc[c][3 * CT + 4]);
               uint32_t* o = reinterpret_cast<uint32_t*>(recc(c) + static_cast<size_t>(y * 8 - 1) * cw + x * 8);
@@ -388,9 +476,9 @@ __global__ __launch_bounds__(64 * kDeblockWaves) void deblock_wavefront(DeblockA
             if (rc <= 6 || last_row) {
               const uint32_t* ti = reinterpret_cast<const uint32_t*>(&S.tc[c][(rc + 4) * CT]);
               uint32_t* o = reinterpret_cast<uint32_t*>(recc(c) + static_cast<size_t>(y * 8 + rc) * cw + x * 8);
-              o[0] = ti[1];                   // own cols 0..3
-              if (last_col) o[1] = ti[2];     // own cols 4..7
-              if (has_left) o[-1] = ti[0];    // left MB's cols 4..7
+              if (st_own) o[0] = ti[1];                 // own cols 0..3
+              if (last_col && st_own) o[1] = ti[2];     // own cols 4..7
+              if (has_left && st_left) o[-1] = ti[0];   // left MB's cols 4..7
             }
           }
         }
@@ -438,11 +526,10 @@ __global__ __launch_bounds__(64 * kDeblockWaves) void deblock_wavefront(DeblockA
         else S.left_c[ccomp][cline] = *reinterpret_cast<const uint32_t*>(&S.tc[ccomp][(cline + 4) * CT + 8]);
         if (hl < 12) S.bot_y[hl / 3][hl % 3] = *reinterpret_cast<const uint32_t*>(&S.ty[(hl / 3 + 16) * LT + 4 + 4 * (hl % 3)]);
         else if (hl < 16) { const int i = hl - 12; S.bot_c[i >> 1][i & 1] = *reinterpret_cast<const uint32_t*>(&S.tc[i >> 1][((i & 1) + 10) * CT + 4]); }
-        else if (hl < 28) S.hdrw[1][hl - 16] = S.hdrw[0][hl - 16];
-        else S.nzw[1][hl - 28] = S.nzw[0][hl - 28];
         wave_sync();
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
         if (hl == 0) __hip_atomic_store(prog + y, x + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        left_quiet = ((inf_q >> kInfoOnShift) & 255u) == 0;
       }
     }
   }
@@ -453,8 +540,24 @@ __global__ __launch_bounds__(64 * kDeblockWaves) void deblock_wavefront(DeblockA
 
 using namespace mivc::gpu;
 
+// encoder pre-pass: records -> strengths [B, nmb, 16] and info words [B, nmb]
+extern "C" void mivc_launch_deblock_bs(int B, int wmb, int hmb, const void* hdr, const uint8_t* nz, uint8_t* bs,
+                                       uint32_t* info, void* stream, const void* route) {
+  DeblockBsArgs a;
+  a.g = Geom{B, wmb, hmb, wmb * 16, hmb * 16};
+  a.hdr = static_cast<const mivc::h264::MbHeader*>(hdr);
+  a.nz = nz;
+  a.bs = bs;
+  a.info = info;
+  a.rt = static_cast<const SlotRoute*>(route);
+  const int per = kBsThreads / 8;
+  hipLaunchKernelGGL(deblock_bs, dim3((a.g.nmb() + per - 1) / per, B), dim3(kBsThreads), 0,
+                     static_cast<hipStream_t>(stream), a);
+}
+
+// encoder: bs / info are what mivc_launch_deblock_bs wrote for these records, earlier on this stream
 extern "C" void mivc_launch_deblock(int B, int wmb, int hmb, uint8_t* rec_y, uint8_t* rec_u, uint8_t* rec_v,
-                                    const void* hdr, const uint8_t* nz, int chroma_qp_offset, int alpha_off,
+                                    const uint8_t* bs, const uint32_t* info, int chroma_qp_offset, int alpha_off,
                                     int beta_off, int* err, void* stream, const void* route, int nbuf) {
   DeblockArgs a;
   a.rt = static_cast<const SlotRoute*>(route);
@@ -463,23 +566,25 @@ extern "C" void mivc_launch_deblock(int B, int wmb, int hmb, uint8_t* rec_y, uin
   a.rec_y = rec_y;
   a.rec_u = rec_u;
   a.rec_v = rec_v;
-  a.hdr = static_cast<const mivc::h264::MbHeader*>(hdr);
-  a.nz = nz;
   a.chroma_qp_offset = chroma_qp_offset;
   a.alpha_off = alpha_off;
   a.beta_off = beta_off;
   a.err = err;
-  a.bs_in = nullptr;
+  a.bs_in = bs;
+  a.info = info;
+  a.hdr = nullptr;
   a.dpb_n = 0;
   a.cur_idx = nullptr;
   hipLaunchKernelGGL(deblock_wavefront, dim3(B), dim3(64 * kDeblockWaves), 0, static_cast<hipStream_t>(stream), a);
 }
 
 // decoder: filter picture cur_idx[slot] of each slot's DPB with the parser's boundary strengths
+// (no info words: the wavefront reads the QPs from the records)
 extern "C" void mivc_launch_deblock_dpb(int B, int wmb, int hmb, int dpb_n, uint8_t* dpb_y, uint8_t* dpb_u,
                                         uint8_t* dpb_v, const int16_t* cur_idx, const void* hdr, const uint8_t* nz,
                                         const uint8_t* bs, int chroma_qp_offset, int alpha_off, int beta_off, int* err,
                                         void* stream) {
+  (void)nz;
   DeblockArgs a;
   a.rt = nullptr;
   a.nbuf = 0;
@@ -487,13 +592,13 @@ extern "C" void mivc_launch_deblock_dpb(int B, int wmb, int hmb, int dpb_n, uint
   a.rec_y = dpb_y;
   a.rec_u = dpb_u;
   a.rec_v = dpb_v;
-  a.hdr = static_cast<const mivc::h264::MbHeader*>(hdr);
-  a.nz = nz;
   a.chroma_qp_offset = chroma_qp_offset;
   a.alpha_off = alpha_off;
   a.beta_off = beta_off;
   a.err = err;
   a.bs_in = bs;
+  a.info = nullptr;
+  a.hdr = static_cast<const mivc::h264::MbHeader*>(hdr);
   a.dpb_n = dpb_n;
   a.cur_idx = cur_idx;
   hipLaunchKernelGGL(deblock_wavefront, dim3(B), dim3(64 * kDeblockWaves), 0, static_cast<hipStream_t>(stream), a);

@@ -487,6 +487,12 @@ class GpuH264Encoder:
         self.hdr = [torch.zeros((B, nmb, MB_HDR_BYTES), dtype=u8, device=dev) for _ in range(2)]
         self.coef = [torch.zeros((B, nmb, COEF_PER_MB), dtype=i16, device=dev) for _ in range(2)]
         self.nz = torch.zeros((B, nmb, 16), dtype=u8, device=dev)
+        # the in-loop filter's boundary strengths and info words (deblock_bs, a pre-pass of the
+        # deblocking wavefront; a kernel library from before it derives them in the wavefront)
+        self.dbk_bs = self.dbk_info = None
+        if hasattr(self.hip, "deblock_bs"):
+            self.dbk_bs = torch.zeros((B, nmb, 16), dtype=u8, device=dev)
+            self.dbk_info = torch.zeros((B, nmb), dtype=i32, device=dev)
         self.mv = torch.zeros((B, nmb, 2), dtype=i16, device=dev)
         self.mv_tmp = torch.zeros((B, nmb, 2), dtype=i16, device=dev)
         self.mv8 = torch.zeros((B, nmb, 4, 2), dtype=i16, device=dev)   # P partition vectors
@@ -933,7 +939,11 @@ class GpuH264Encoder:
         # only with --full-recon): the routing flags SF_DEBLOCK accordingly.
         if self.p.deblock and st["deblock"]:
             with stt("deblock"):
-                self.hip.deblock(B, wmb, hmb, py, pu, pv, P(hdr), P(self.nz), cqo, 0, 0, P(self.err), s, rt, NB)
+                dkw = {}
+                if self.dbk_bs is not None:
+                    dkw = dict(bs=P(self.dbk_bs), info=P(self.dbk_info))
+                    self.hip.deblock_bs(B, wmb, hmb, P(hdr), P(self.nz), dkw["bs"], dkw["info"], s, rt)
+                self.hip.deblock(B, wmb, hmb, py, pu, pv, P(hdr), P(self.nz), cqo, 0, 0, P(self.err), s, rt, NB, **dkw)
         if st["ref"]:
             # the reference pictures' half-sample planes (shared by every picture predicting from
             # them) and, for B pictures, their records as co-located candidates

@@ -12,7 +12,9 @@ tests/test_gpu_inter_block_mask.py (suite ``mask``: the block masks the inter ke
 GPU CABAC path, which the parent's kernels do not write: its bytes, with the record statistics per
 case) and tests/test_gpu_me_uniform_encode.py (suite ``me``: whole encodes through the 16x16 motion
 search, whose wave-uniform work moved to the scalar unit: P only, B pictures with temporal direct,
-three references with weighted P, b-pyramid, CAVLC, one HEVC encode).
+three references with weighted P, b-pyramid, CAVLC, one HEVC encode) and
+tests/test_gpu_deblock_encode.py (suite ``deblock``: whole encodes through the in-loop filter, with
+the hash of the kept reconstruction per slot).
 
 The tests pin the bytes of small encodes, at shapes where the four-MBs-per-wave lane layout can
 go wrong, to what the *parent* build of the kernels emits.  So this recorder never runs on the
@@ -29,6 +31,7 @@ commit, e.g.
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py bfetch tests/golden/b_block_fetch_parent.json
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py mask tests/golden/inter_block_mask_parent.json
     MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py me tests/golden/me_uniform_parent.json
+    MIVC_HIP_LIB=abso/parent.so python tools/record_inter_layout.py deblock tests/golden/deblock_bs_parent.json
 
 The file holds, per case, the arguments (size, frames, clip seed / class, parameter overrides)
 and the SHA-256 of every slot's bitstream.  Per case it also prints what the test asserts
@@ -587,6 +590,28 @@ def record_mask(host, path) -> None:
         f.write("\n")
 
 
+def record_deblock(host, path) -> None:
+    """Suite ``deblock``: per case the per-slot hashes of the bitstream and of the kept
+    reconstruction (every picture filtered), with the share of P-picture MBs whose 32 boundary
+    strengths are all zero (from the parser).  The cases and the clips are the test's own."""
+    import numpy as np
+    from tests import test_gpu_deblock_encode as T
+
+    rows = []
+    for case in T.CASES:
+        case = json.loads(json.dumps(case))  # as the test will read it
+        streams, recon, bs = T.encode(case)
+        if bs:
+            raise SystemExit("this kernel library has the deblocking pre-pass: not the parent's")
+        quiet = [float((np.asarray(seg["bs"])[np.asarray(seg["meta"])[:, 4] % 5 == 0] == 0).all(axis=2).mean())
+                 for seg in host.parse(streams, 1)]
+        print(case["id"], [len(s) for s in streams], "quiet MBs of P pictures", [round(q, 3) for q in quiet], flush=True)
+        rows.append(dict(case, **T.hashes(streams, recon)))
+    with open(path, "w") as f:
+        json.dump(dict(slots=SLOTS, cases=rows), f, indent=1)
+        f.write("\n")
+
+
 def np_isin_any(a, values) -> bool:
     import numpy as np
 
@@ -595,7 +620,8 @@ def np_isin_any(a, values) -> bool:
 
 def main() -> None:
     suite = "inter"
-    if len(sys.argv) == 3 and sys.argv[1] in ("inter", "decide", "gate", "intra", "source", "chroma8", "bfetch", "mask", "me"):
+    if len(sys.argv) == 3 and sys.argv[1] in ("inter", "decide", "gate", "intra", "source", "chroma8", "bfetch", "mask", "me",
+                                              "deblock"):
         suite = sys.argv.pop(1)
     if len(sys.argv) != 2:
         raise SystemExit(__doc__)
@@ -620,6 +646,9 @@ def main() -> None:
         return
     if suite == "mask":
         record_mask(host, sys.argv[1])
+        return
+    if suite == "deblock":
+        record_deblock(host, sys.argv[1])
         return
     if suite == "gate":
         for case in GATE_CASES:
