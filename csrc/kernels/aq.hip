@@ -25,6 +25,7 @@
 
 #include "aq_auto.h"
 #include "kcommon.h"
+#include "launch.h"
 
 namespace mivc {
 namespace gpu {

@@ -30,6 +30,7 @@
 // throughput scales with the number of independent slices in flight: grouping G frame
 // steps multiplies the waves the chip runs at once by G.
 #include "kcommon.h"
+#include "launch.h"
 // after kcommon.h: the shared headers' MIVC_HD needs the HIP runtime declarations
 #include "../common/h264_cabac.h"
 

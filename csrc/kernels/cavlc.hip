@@ -22,6 +22,7 @@
 //   cavlc_compact   (B, 256)                  big-endian words -> bytes, packed slot after slot
 #include "h264_mvpred.h"
 #include "kcommon.h"
+#include "launch.h"
 
 namespace mivc {
 namespace gpu {

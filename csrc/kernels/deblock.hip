@@ -12,6 +12,7 @@
 // records (intra, non-zero coefficients, motion vectors) by a parallel pre-pass,
 // deblock_bs; the wavefront skips what they switch off.
 #include "kcommon.h"
+#include "launch.h"
 
 namespace mivc {
 namespace gpu {
@@ -65,7 +66,6 @@ constexpr int kRingU = 4;       // bottom-edge slots from a wave's upper half to
 constexpr int LT = 20;          // luma tile stride: 4 halo + 16 (rows -4..15, cols -4..15)
 constexpr int CT = 12;          // chroma tile stride: 4 halo + 8 (rows -4..7, cols -4..7)
 constexpr int kSlotWords = 24;  // luma rows 12..15 (16 words) + Cb/Cr rows 6..7 (2 x 4 words)
-constexpr int kMaxCols = 480;   // MB columns (8K: 7680 / 16)
 
 // Layout.  Wave w deblocks MB rows 2w + 32k (upper half-wave, lanes
 // 0..31) and 2w + 32k + 1 (lower half, lanes 32..63) in lock step, the lower half two MBs
@@ -581,10 +581,8 @@ extern "C" void mivc_launch_deblock(int B, int wmb, int hmb, uint8_t* rec_y, uin
 // decoder: filter picture cur_idx[slot] of each slot's DPB with the parser's boundary strengths
 // (no info words: the wavefront reads the QPs from the records)
 extern "C" void mivc_launch_deblock_dpb(int B, int wmb, int hmb, int dpb_n, uint8_t* dpb_y, uint8_t* dpb_u,
-                                        uint8_t* dpb_v, const int16_t* cur_idx, const void* hdr, const uint8_t* nz,
-                                        const uint8_t* bs, int chroma_qp_offset, int alpha_off, int beta_off, int* err,
-                                        void* stream) {
-  (void)nz;
+                                        uint8_t* dpb_v, const int16_t* cur_idx, const void* hdr, const uint8_t* bs,
+                                        int chroma_qp_offset, int alpha_off, int beta_off, int* err, void* stream) {
   DeblockArgs a;
   a.rt = nullptr;
   a.nbuf = 0;

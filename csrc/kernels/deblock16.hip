@@ -21,6 +21,7 @@
 // counts as 0 (the parser's records carry that) --, the average indexes the tables clipped
 // to 0..51, alpha' / beta' / tC0' are scaled by 1 << (bd - 8), clips go to (1 << bd) - 1.
 #include "kcommon.h"
+#include "launch.h"
 
 namespace mivc {
 namespace gpu {

@@ -32,6 +32,7 @@
 // Reference parity: the reference decodes with ffmpeg inside the worker
 // (client.go:115-118); the CPU decoder (h264_decoder.cc) is the bit-exact oracle.
 #include "h264_t8.h"
+#include "launch.h"
 #include "../common/h264_cabac_tables.h"
 
 namespace mivc {

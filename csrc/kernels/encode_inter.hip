@@ -11,6 +11,7 @@
 // per wave (one 16-lane row per MB, a lane per 4x4 block: encode_inter_mb), then chroma eight
 // per wave (eight lanes per MB: encode_inter_chroma).
 #include "h264_trellis.h"
+#include "launch.h"
 #include "mb_row.h"
 
 namespace mivc {

@@ -19,6 +19,7 @@
 // of it reads what another writes; the stream order between the two launches is the only
 // ordering across workgroups.
 #include "h264_trellis.h"
+#include "launch.h"
 #include "../common/h264_i4_taps.h"
 
 #include <atomic>

@@ -3,6 +3,7 @@
 // limited range, ops/scale.py rgb_to_i420).  Resampling (`-s WxH`, server.go:87-90)
 // is the bicubic filter of scale.hip.  SURVEY.md K-C2 (csc_scale).
 #include "kcommon.h"
+#include "launch.h"
 
 namespace mivc {
 namespace gpu {

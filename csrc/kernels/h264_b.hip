@@ -27,6 +27,7 @@
 //                                    decoding-order pass makes it exact, a parallel pass re-predicts
 #include "h264_mvpred.h"
 #include "kcommon.h"
+#include "launch.h"
 #include "mb_row.h"
 #include "qpel.h"
 
@@ -700,7 +701,6 @@ struct BSpatialArgs {
 };
 
 
-constexpr int kSpatialMaxCols = 480;  // MB columns (8K)
 constexpr int kSpatialWaves = 16;  // 16 row chains per slot: the chain (wmb + 2 hmb MBs) bounds it, not the MB count
 
 // packed motion of one quadrant and list: ref (low 8 bits, signed) | mvx << 8 (12 bits) |
@@ -733,7 +733,7 @@ __global__ __launch_bounds__(64 * kSpatialWaves) void b_spatial_decide(BSpatialA
   if (!route_active(a.rt, slot, SK_B)) return;  // uniform per workgroup
   __shared__ int prog[kMaxRows];
   __shared__ int s_res[kSpatialWaves][2][256];
-  __shared__ int nbq[2][kSpatialMaxCols][5];  // [row parity][column]: intra, L0 q2, L0 q3, L1 q2, L1 q3
+  __shared__ int nbq[2][kMaxCols][5];  // [row parity][column]: intra, L0 q2, L0 q3, L1 q2, L1 q3
   for (int i = threadIdx.x; i < g.hmb; i += blockDim.x) prog[i] = 0;
   __syncthreads();
   const int w = wave_id(), lane = lane_id();
@@ -948,13 +948,11 @@ struct BSpatialExactArgs {
   int tol;
 };
 
-constexpr int kExactWaves = 5;  // one lane per MB row: 320 >= 8K's 270 rows
-
 __global__ __launch_bounds__(64 * kExactWaves) void b_spatial_exact(BSpatialExactArgs a) {
   const Geom& g = a.g;
   const int slot = blockIdx.x, nmb = g.nmb(), wmb = g.wmb, hmb = g.hmb;
   if (!route_active(a.rt, slot, SK_B)) return;  // uniform per workgroup
-  __shared__ int nbq[2][kSpatialMaxCols][5];      // [row parity][column]: intra, L0 q2, L0 q3, L1 q2, L1 q3
+  __shared__ int nbq[2][kMaxCols][5];      // [row parity][column]: intra, L0 q2, L0 q3, L1 q2, L1 q3
   const int y = threadIdx.x;
   const bool row_ok = y < hmb;
   MbHeader* H = a.hdr + static_cast<size_t>(slot) * nmb;

@@ -4,6 +4,7 @@
 //                                     (and the 8x8 inter CUs of HEVC P pictures)
 #include "h264_mvpred.h"
 #include "kcommon.h"
+#include "launch.h"
 #include "mb_row.h"
 #include "qpel.h"
 

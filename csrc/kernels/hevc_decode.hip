@@ -20,6 +20,7 @@
 //   hevcd_sao        band / edge offsets per CTB from the deblocked copy
 #include "hevc_common.h"
 #include "hevc_decode.h"
+#include "launch.h"
 
 namespace mivc {
 namespace gpu {

@@ -20,6 +20,7 @@
 
 #include "../common/hevc_ctu_coder.h"
 #include "kcommon.h"
+#include "launch.h"
 
 namespace mivc {
 namespace gpu {

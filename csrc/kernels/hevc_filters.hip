@@ -14,6 +14,7 @@
 // estimate, stores the parameters for the CABAC writer and applies them.
 #include "aq_auto.h"
 #include "kcommon.h"
+#include "launch.h"
 #include "../common/hevc_tables.h"
 
 namespace mivc {

@@ -15,6 +15,7 @@
 //   inter rounding offset, reconstruction.  No dependency between CUs: fully
 //   parallel; the intra CUs of the picture are then coded by hevc_intra_recon.
 #include "hevc_inter_cu.h"
+#include "launch.h"
 
 namespace mivc {
 namespace gpu {

@@ -15,6 +15,7 @@
 //   CUs are visited (inter CUs were reconstructed by hevc_inter).
 #include "hevc_common.h"
 #include "hevc_tskip.h"
+#include "launch.h"
 
 namespace mivc {
 namespace gpu {

@@ -3,6 +3,7 @@
 // planes and stores the prediction.  Kernel and numpy model (tests/ref_models_hevc_wp.py) meet
 // here on planted planes, vectors and weights instead of only through whole encodes.
 #include "hevc_mc.h"
+#include "launch.h"
 
 namespace mivc {
 namespace gpu {

@@ -4,6 +4,7 @@
 //   hevc_b_init_p     (thread per block)      P pictures enter the merge passes in B form
 //   hevc_b_merge      (four blocks per wave)  the writer's exact merge list per block (Jacobi)
 #include "kcommon.h"
+#include "launch.h"
 #include "mb_row.h"
 #include "qpel.h"
 #include "../common/hevc_tables.h"

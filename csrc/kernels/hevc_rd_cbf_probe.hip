@@ -6,6 +6,7 @@
 // Kernel and numpy model (tests/ref_models_hevc_rdcbf.py) meet here on planted blocks.
 #include "hevc_common.h"
 #include "hevc_rdcbf.h"
+#include "launch.h"
 
 namespace mivc {
 namespace gpu {

@@ -4,6 +4,7 @@
 // residual and the returned flag.  Kernel and numpy model (tests/ref_models_hevc_rdoq.py) meet
 // here on planted blocks instead of only through whole encodes.
 #include "hevc_common.h"
+#include "launch.h"
 
 namespace mivc {
 namespace gpu {

@@ -5,6 +5,7 @@
 // transform_skip_flag, the cbf and the terms of the comparison.  Kernel and numpy model
 // (tests/ref_models_hevc_tskip.py) meet here on planted blocks.
 #include "hevc_tskip.h"
+#include "launch.h"
 
 namespace mivc {
 namespace gpu {

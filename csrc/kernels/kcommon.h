@@ -7,6 +7,7 @@
 #include "../common/h264_mb.h"
 #include "../common/h264_pred.h"
 #include "../common/h264_tables.h"
+#include "geom_limits.h"
 #include "route.h"
 
 namespace mivc {
@@ -104,8 +105,8 @@ __device__ __forceinline__ int satd4x4_u8(const uint32_t (&s)[4], const uint32_t
 // its vector L1, so release/acquire at workgroup scope is an s_waitcnt, not a
 // cache write-back/invalidate (agent-scope fences cost 1.7-7 us per hand-off on
 // MI355X, guide §Persistent kernels price list; the first version of these
-// kernels spent ~20 us per MB step there).
-constexpr int kMaxRows = 272;  // 8K: 4320 / 16 = 270 MB rows
+// kernels spent ~20 us per MB step there).  The progress arrays hold kMaxRows rows
+// (geom_limits.h).
 
 // Keep memory freed with hipFreeAsync in the device's default pool (release threshold
 // "never"): by default the pool hands it back to the driver at every synchronisation, and

@@ -33,6 +33,7 @@
 // operand (H64, 4 row tiles of 16) is generated in registers.  SADs of the search
 // are summed over the four row groups of a column with two v_permlane{16,32}_swap.
 #include "kcommon.h"
+#include "launch.h"
 #include "qpel.h"
 
 namespace mivc {

@@ -18,6 +18,7 @@
 // per-MB QPs and the bitstream -- are identical from run to run (a float atomicAdd sum
 // depends on the order the waves arrive in).
 #include "kcommon.h"
+#include "launch.h"
 
 namespace mivc {
 namespace gpu {

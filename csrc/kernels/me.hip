@@ -1,5 +1,6 @@
 // Motion estimation launchers and the kernels around the search (me_search.h): the frame-level
 // half-sample planes, the ungated search instances and the reference selection of P macroblocks.
+#include "launch.h"
 #include "me_search.h"
 
 #include <cstdio>

@@ -2,6 +2,7 @@
 // source and the deblocked reconstruction over the display window, per plane,
 // plus an 8x8-window SSIM sum on luma.  PSNR/SSIM are finished on the host.
 #include "h264_trellis.h"
+#include "launch.h"
 
 namespace mivc {
 namespace gpu {

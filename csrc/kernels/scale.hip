@@ -15,6 +15,7 @@
 // coded-size padding of the encoders) replicate the last display column / row.
 // 8-bit (uint8) and 10-bit (uint16) samples; frames along grid z.
 #include "kcommon.h"
+#include "launch.h"
 
 namespace mivc {
 namespace gpu {

@@ -27,6 +27,7 @@
 #include <algorithm>
 
 #include "kcommon.h"
+#include "launch.h"
 
 namespace mivc {
 namespace gpu {

@@ -18,6 +18,7 @@
 //              kernels run unchanged against the weighted proxies: each approximates the current
 //              picture, and their plain average the explicit bi-prediction.
 #include "kcommon.h"
+#include "launch.h"
 
 namespace mivc {
 namespace gpu {

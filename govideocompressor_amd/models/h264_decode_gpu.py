@@ -75,11 +75,6 @@ _META = ("pic_id", "ref_id", "nal_ref", "idr", "slice_type", "slice_qp", "alpha"
 M = {k: i for i, k in enumerate(_META)}
 
 
-# deblock16.hip and decode.hip's intra wavefront (either depth) keep row progress counters for
-# this many MB rows (kMaxRows)
-_MAX_MB_ROWS_16 = 272
-
-
 def _gpu_plan(seg: dict, high_depth: str = "cpu") -> tuple[bool, str]:
     """Can the GPU path reconstruct this parsed segment?  ``high_depth="gpu"``: 9- and 10-bit
     segments too (the parser's ``gpu_ok16``: ``gpu_ok`` but for the bit depth)."""
@@ -87,11 +82,16 @@ def _gpu_plan(seg: dict, high_depth: str = "cpu") -> tuple[bool, str]:
         return False, seg["error"]
     if seg["n"] == 0:
         return False, "no pictures"
+    # the intra and deblocking wavefronts (either depth) keep row progress counters, and the
+    # 8-bit deblocking a ring of bottom edges per MB column, for a picture of this size at most
+    max_rows, max_cols = native.kernel_limits()
+    if seg["coded_height"] // 16 > max_rows:
+        return False, "too many macroblock rows"
+    if seg["coded_width"] // 16 > max_cols:
+        return False, "too many macroblock columns"
     if high_depth == "gpu" and int(seg["bit_depth"]) > 8:
         if not np.all(seg["gpu_ok16"] == 1):
             return False, "unsupported coding tools"
-        if seg["coded_height"] // 16 > _MAX_MB_ROWS_16:
-            return False, "too many macroblock rows"
         return True, ""
     if not np.all(seg["meta"][:, M["gpu_ok"]] == 1):
         return False, "unsupported coding tools"

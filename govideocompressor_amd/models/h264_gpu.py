@@ -450,6 +450,10 @@ class GpuH264Encoder:
             raise RuntimeError("aq_mode 2 / 3 need a kernel library with the auto-variance AQ kernels (rebuild)")
         self.wmb = (params.width + 15) // 16
         self.hmb = (params.height + 15) // 16
+        self.max_mb_rows, max_mb_cols = native.kernel_limits()
+        if self.hmb > self.max_mb_rows or self.wmb > max_mb_cols:
+            raise ValueError(f"{params.width}x{params.height} is {self.wmb} x {self.hmb} macroblocks: the intra and "
+                             f"deblocking kernels take at most {max_mb_cols} x {self.max_mb_rows}")
         self.W, self.H = self.wmb * 16, self.hmb * 16
         self.nmb = self.wmb * self.hmb
         self._mbtree = None  # [B, F, nmb] MB-tree QP offsets of the batch being encoded
@@ -913,9 +917,9 @@ class GpuH264Encoder:
         trial = not inter or self.p.i4x4_in_p or cut is not None
         if getattr(self, "_intra_prog", None) is None:
             # cross-workgroup row progress of the multi-workgroup I-picture wavefront (this
-            # encoder's own: [slice units][kMaxRows = 272] ints, zeroed by the launcher on `s`)
+            # encoder's own: [slice units][kMaxRows] ints, zeroed by the launcher on `s`)
             per = -(-hmb // self.slice_rows) if self.slice_rows > 0 else 1
-            self._intra_prog = torch.zeros(B * per * 272, dtype=torch.int32, device=self.dev)
+            self._intra_prog = torch.zeros(B * per * self.max_mb_rows, dtype=torch.int32, device=self.dev)
         with stt("intra"):
             self.hip.encode_intra(B, wmb, hmb, sy, su, sv, py, pu, pv, P(self.qp), cqo, P(hdr), P(coef), P(self.nz),
                                   flag_ptr, count_ptr, P(self.err), int(self.p.i4x4 and trial), s, aq,

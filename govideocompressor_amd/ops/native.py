@@ -68,6 +68,14 @@ def hip():
         ) from e
 
 
+def kernel_limits() -> tuple[int, int]:
+    """``(max_mb_rows, max_mb_cols)``: the largest picture, in macroblocks, of the kernels that
+    index fixed LDS arrays by row or column (csrc/kernels/geom_limits.h; the bindings refuse
+    more).  A library from before the attributes (``MIVC_HIP_LIB``) was built with these values."""
+    lib = hip()
+    return int(getattr(lib, "max_mb_rows", 272)), int(getattr(lib, "max_mb_cols", 480))
+
+
 def gpu_available() -> bool:
     try:
         import torch
