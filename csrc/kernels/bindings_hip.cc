@@ -98,6 +98,31 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("B"), py::arg("wmb"), py::arg("hmb"), py::arg("nref"), py::arg("mv"), py::arg("mv8"), py::arg("cost"),
      py::arg("pred"), py::arg("xmv"), py::arg("xcost"), py::arg("xpred"), py::arg("mref"), py::arg("qp"), py::arg("aq"),
      py::arg("stream"), py::arg("route") = 0);
+  m.def("p_mixed_refs", [](int B, int wmb, int hmb, int nref, uintptr_t mv, uintptr_t mv8, uintptr_t cost,
+                           uintptr_t pred, uintptr_t xmv, uintptr_t xcost, uintptr_t xpred, uintptr_t mref,
+                           uintptr_t mref4, uintptr_t qp, uintptr_t aq, uintptr_t src0, uintptr_t src, uintptr_t ref,
+                           uintptr_t hp, uintptr_t pm, uintptr_t scale, int overhead, int min_satd, uintptr_t stream,
+                           uintptr_t route, int nbuf) {
+    // mixed references per 8x8 partition (h264_p_mixed.hip): me_ref_select's arguments, the sources
+    // (src0: what the list-0[0] searches saw), the reference and half-sample pools, the ME's
+    // predictor and the distance scales (int16 [nref - 1, B], 1/256 units); indexes no fixed array
+    if (B < 1 || wmb < 1 || hmb < 1) throw std::invalid_argument("p_mixed_refs: bad geometry");
+    if (nref < 2 || nref > 4) throw std::invalid_argument("p_mixed_refs: nref in 2..4");
+    if (!route || nbuf < 1) throw std::invalid_argument("p_mixed_refs: a routed launch (the pictures are pool buffers)");
+    if (!mv || !mv8 || !cost || !pred || !xmv || !xcost || !xpred || !mref || !mref4 || !qp || !src0 || !src || !ref ||
+        !hp || !pm || !scale)
+      throw std::invalid_argument("p_mixed_refs: null buffer");
+    if ((mv | mref4 | pred | xpred | src0 | src) & 3) throw std::invalid_argument("p_mixed_refs: mv, mref4, pred, xpred and the sources are read as words");
+    if (mv8 & 15) throw std::invalid_argument("p_mixed_refs: mv8 must be 16-byte aligned");
+    mivc_launch_p_mixed_refs(B, wmb, hmb, nref, P<int16_t>(mv), P<int16_t>(mv8), P<int>(cost), P<uint8_t>(pred),
+                             P<int16_t>(xmv), P<int>(xcost), P<uint8_t>(xpred), P<int8_t>(mref), P<int8_t>(mref4),
+                             P<int>(qp), P<int8_t>(aq), P<uint8_t>(src0), P<uint8_t>(src), P<uint8_t>(ref),
+                             P<uint8_t>(hp), P<int16_t>(pm), P<int16_t>(scale), overhead, min_satd, S(stream),
+                             P<void>(route), nbuf);
+  }, py::arg("B"), py::arg("wmb"), py::arg("hmb"), py::arg("nref"), py::arg("mv"), py::arg("mv8"), py::arg("cost"),
+     py::arg("pred"), py::arg("xmv"), py::arg("xcost"), py::arg("xpred"), py::arg("mref"), py::arg("mref4"),
+     py::arg("qp"), py::arg("aq"), py::arg("src0"), py::arg("src"), py::arg("ref"), py::arg("hp"), py::arg("pm"),
+     py::arg("scale"), py::arg("overhead"), py::arg("min_satd"), py::arg("stream"), py::arg("route"), py::arg("nbuf"));
   m.def("b_spatial", [](int B, int wmb, int hmb, uintptr_t hdr, uintptr_t col, uintptr_t src, uintptr_t ref1,
                         uintptr_t hp1, std::vector<uintptr_t> ref0k, std::vector<uintptr_t> hp0k, std::vector<int> w1,
                         uintptr_t pred_out, uintptr_t err, uintptr_t stream, uintptr_t intra_cost, uintptr_t cost,
@@ -277,9 +302,13 @@ PYBIND11_MODULE(_hip, m) {
            uintptr_t intra_flag, uintptr_t intra_count, uintptr_t stream, uintptr_t aq, uintptr_t ref1_u,
            uintptr_t ref1_v, int bmode, int t8, uintptr_t mv8, std::vector<int> w1, std::vector<uintptr_t> xref_u,
            std::vector<uintptr_t> xref_v, uintptr_t mref, uintptr_t wp, int trellis, float trellis_lambda,
-           uintptr_t route, int nbuf, uintptr_t qp_flags, uintptr_t mask_pre) {
+           uintptr_t route, int nbuf, uintptr_t qp_flags, uintptr_t mask_pre, uintptr_t mref4) {
           // mask_pre: uint32 [B, nmb], every coded MB's CABAC block mask (cabac_bin's pre)
           if (mask_pre & 3) throw std::invalid_argument("encode_inter: mask_pre must be 4-byte aligned");
+          // mref4: int8 [B, nmb, 4], the reference of every quadrant of a P MB (p_mixed_refs), read as one word
+          if (mref4 & 3) throw std::invalid_argument("encode_inter: mref4 must be 4-byte aligned");
+          if (mref4 && (bmode || !mv8 || !mref))
+            throw std::invalid_argument("encode_inter: mref4 goes with P pictures, mv8 and mref");
           // xref_u / xref_v: chroma of RefPicList0[1..]; w1: implicit list-1 weight per list-0 picture
           if (bmode && (!ref1_u || !ref1_v)) throw std::invalid_argument("encode_inter: B mode needs the list-1 chroma");
           const size_t n = xref_u.size() + 1;
@@ -302,7 +331,7 @@ PYBIND11_MODULE(_hip, m) {
                                    P<int>(intra_count), P<int8_t>(aq), P<uint8_t>(ref1_u), P<uint8_t>(ref1_v), bmode,
                                    t8, P<int16_t>(mv8), S(stream), w.data(), static_cast<int>(n), xu, xv,
                                    bmode ? nullptr : P<int8_t>(mref), P<int>(wp), trellis, trellis_lambda, P<void>(route),
-                                   nbuf, P<uint8_t>(qp_flags), P<uint32_t>(mask_pre));
+                                   nbuf, P<uint8_t>(qp_flags), P<uint32_t>(mask_pre), P<int8_t>(mref4));
         }, py::arg("B"), py::arg("wmb"), py::arg("hmb"), py::arg("sy"), py::arg("su"), py::arg("sv"), py::arg("fy"),
         py::arg("fu"), py::arg("fv"), py::arg("ry"), py::arg("ru"), py::arg("rv"), py::arg("pred"), py::arg("mv"),
         py::arg("me_cost"), py::arg("intra_cost"), py::arg("qp"), py::arg("cqo"), py::arg("hdr"), py::arg("coef"),
@@ -311,7 +340,7 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("w1") = std::vector<int>{32}, py::arg("xref_u") = std::vector<uintptr_t>{},
         py::arg("xref_v") = std::vector<uintptr_t>{}, py::arg("mref") = 0, py::arg("wp") = 0, py::arg("trellis") = 0,
         py::arg("trellis_lambda") = 1.0f, py::arg("route") = 0, py::arg("nbuf") = 0, py::arg("qp_flags") = 0,
-        py::arg("mask_pre") = 0);
+        py::arg("mask_pre") = 0, py::arg("mref4") = 0);
   m.def("wp_stats16", [](uintptr_t y, uintptr_t u, uintptr_t v, int w, int h, int npics, uintptr_t out, uintptr_t stream) {
     if (w % 2 || h % 2 || npics <= 0) throw std::invalid_argument("wp_stats16: even picture sizes, npics > 0");
     mivc_launch_wp_stats16(P<uint16_t>(y), P<uint16_t>(u), P<uint16_t>(v), w, h, npics, P<unsigned long long>(out),

@@ -10,6 +10,15 @@
 // SURVEY.md K-C8.  Two launches, every lane of a wave64 at work in both: luma four macroblocks
 // per wave (one 16-lane row per MB, a lane per 4x4 block: encode_inter_mb), then chroma eight
 // per wave (eight lanes per MB: encode_inter_chroma).
+//
+// This file is compiled twice.  On its own it is the default kernels and the launcher.  With
+// MIVC_INTER_MIXED_UNIT defined (encode_inter_mixed.hip includes it) it is the instances for P
+// pictures with a reference per 8x8 quadrant (x264 --mixed-refs): encode_inter_mb_mixed and
+// encode_inter_chroma_mixed take mref4 [B, nmb, 4], p_mixed_refs' choice (h264_p_mixed.hip) --
+// the explicit weight applies to the quadrants on reference 0 only, chroma block cb predicts from
+// its quadrant's picture, the record takes ref[0][q] = mref4[q], and quadrants pair into P_16x8 /
+// P_8x16 / P_16x16 only when vector and reference agree.  Every difference sits behind that
+// macro, so the default unit's kernels are compiled from the text they always were.
 #include "h264_trellis.h"
 #include "launch.h"
 #include "mb_row.h"
@@ -200,7 +209,12 @@ __device__ __forceinline__ uint32_t ld4(const uint8_t* row, int x) {
 // stores, and the decimation score is branch-free.  Every wave_sync() sits in wave-uniform
 // control flow; MBs of a wave that are dead (tail), intra-flagged or not on the 8x8 path are
 // masked by per-lane predicates, never by an early exit.
+#ifdef MIVC_INTER_MIXED_UNIT
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void encode_inter_mb_mixed(InterArgs a,
+                                                                                                        const int8_t* mref4) {
+#else
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void encode_inter_mb(InterArgs a) {
+#endif
   const Geom& g = a.g;
   const int lane = threadIdx.x, q = lane >> 4, l = lane & 15;
   const int nmb = g.nmb();
@@ -264,7 +278,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
         prw[y] = *reinterpret_cast<const uint32_t*>(pred + y * 16);
         sw[y] = *reinterpret_cast<const uint32_t*>(srcy + static_cast<size_t>(y) * W);
       }
+#ifdef MIVC_INTER_MIXED_UNIT
+      if (a.wp && !a.bmode && !mref4[o * 4 + (l >> 2)]) {  // weighted RefPicList0[0] prediction, this block's quadrant
+#else
       if (a.wp && !a.bmode && !(a.mref && a.mref[o])) {  // weighted RefPicList0[0] prediction
+#endif
         const int* wt = a.wp + slot * 8;
         const int w = wt[0], wo = wt[1], d = wt[2];
         if (w != (1 << d) || wo != 0) {
@@ -552,11 +570,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
           uint4 q4 = make_uint4(mvw, mvw, mvw, mvw);
           if (a.mv8) q4 = *reinterpret_cast<const uint4*>(a.mv8 + o * 8);
           // quadrant vectors -> the cheapest partition shape that carries them
+#ifdef MIVC_INTER_MIXED_UNIT
+          const uint32_t r = *reinterpret_cast<const uint32_t*>(mref4 + o * 4);  // the four quadrants' references
+          const uint32_t r0 = r & 255u, r1 = (r >> 8) & 255u, r2 = (r >> 16) & 255u, r3 = r >> 24;
+          const bool top = q4.x == q4.y && r0 == r1, bottom = q4.z == q4.w && r2 == r3;
+          const bool left = q4.x == q4.z && r0 == r2, right = q4.y == q4.w && r1 == r3;
+          h->kind = (top && bottom) ? (left ? h264::MBK_P16x16 : h264::MBK_P16x8)
+                                    : ((left && right) ? h264::MBK_P8x16 : h264::MBK_P8x8);
+          uint4* mvp = reinterpret_cast<uint4*>(&h->mv[0][0][0]);  // 16-byte aligned
+          mvp[0] = q4;
+#else
           h->kind = (q4.x == q4.y && q4.z == q4.w) ? (q4.x == q4.z ? h264::MBK_P16x16 : h264::MBK_P16x8)
                                                    : ((q4.x == q4.z && q4.y == q4.w) ? h264::MBK_P8x16 : h264::MBK_P8x8);
           uint4* mvp = reinterpret_cast<uint4*>(&h->mv[0][0][0]);  // 16-byte aligned
           mvp[0] = q4;
           const uint32_t r = a.mref ? static_cast<uint32_t>(a.mref[o]) * 0x01010101u : 0u;
+#endif
           *reinterpret_cast<uint2*>(&h->ref[0][0]) = make_uint2(r, 0xFFFFFFFFu);  // L0 ref r, L1 unused
         }
       }
@@ -573,7 +602,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
 // The component's four DC terms and its AC decimation score are quad DPP reductions, formed
 // by every lane before they are tested; dead MBs of the last wave are clamped to the last MB
 // and masked, never left early.  No LDS.
+#ifdef MIVC_INTER_MIXED_UNIT
+__global__ __launch_bounds__(64) void encode_inter_chroma_mixed(InterArgs a, const int8_t* mref4) {
+#else
 __global__ __launch_bounds__(64) void encode_inter_chroma(InterArgs a) {
+#endif
   const Geom& g = a.g;
   const int lane = threadIdx.x, m = lane >> 3, comp = (lane >> 2) & 1, cb = lane & 3;
   const int nmb = g.nmb();
@@ -616,7 +649,11 @@ __global__ __launch_bounds__(64) void encode_inter_chroma(InterArgs a) {
     if (!a.bmode) {
       // the 4x4 chroma block cb covers luma quadrant cb (its partition's vector)
       const int cmx = a.mv8 ? a.mv8[o * 8 + cb * 2] : a.mv[o * 2], cmy = a.mv8 ? a.mv8[o * 8 + cb * 2 + 1] : a.mv[o * 2 + 1];
+#ifdef MIVC_INTER_MIXED_UNIT
+      const int r = mref4[o * 4 + cb] & 3;
+#else
       const int r = a.mref ? a.mref[o] : 0;
+#endif
       chroma_mc4x4((comp == 0 ? a.refs_u[r] : a.refs_v[r]) + route_index(a.rt, a.nbuf, slot, RO_L0 + r) * g.csize(), cw,
                    CH, px0, py0, cmx, cmy, pp);
       if (a.wp && r == 0) {
@@ -752,9 +789,20 @@ __global__ __launch_bounds__(64) void encode_inter_chroma(InterArgs a) {
   }
 }
 
+#ifdef MIVC_INTER_MIXED_UNIT
+void launch_encode_inter_mixed(const InterArgs& a, const int8_t* mref4, dim3 grid_luma, dim3 grid_chroma, hipStream_t s) {
+  hipLaunchKernelGGL(encode_inter_mb_mixed, grid_luma, dim3(64), 0, s, a, mref4);
+  hipLaunchKernelGGL(encode_inter_chroma_mixed, grid_chroma, dim3(64), 0, s, a, mref4);
+}
+#else
+// the instances with a reference per quadrant (encode_inter_mixed.hip)
+void launch_encode_inter_mixed(const InterArgs& a, const int8_t* mref4, dim3 grid_luma, dim3 grid_chroma, hipStream_t s);
+#endif
+
 }  // namespace gpu
 }  // namespace mivc
 
+#ifndef MIVC_INTER_MIXED_UNIT
 using namespace mivc::gpu;
 
 extern "C" void mivc_launch_encode_inter(int B, int wmb, int hmb, const uint8_t* src_y, const uint8_t* src_u,
@@ -767,7 +815,8 @@ extern "C" void mivc_launch_encode_inter(int B, int wmb, int hmb, const uint8_t*
                                          int t8, const int16_t* mv8, void* stream, const int* w1, int nref,
                                          const uint8_t* const* xref_u, const uint8_t* const* xref_v,
                                          const int8_t* mref, const int* wp, int trellis, float trellis_lambda,
-                                         const void* route, int nbuf, uint8_t* qp_flags, uint32_t* mask_pre) {
+                                         const void* route, int nbuf, uint8_t* qp_flags, uint32_t* mask_pre,
+                                         const int8_t* mref4) {
   InterArgs a;
   a.qp_flags = qp_flags;
   a.mask_pre = mask_pre;
@@ -810,6 +859,12 @@ extern "C" void mivc_launch_encode_inter(int B, int wmb, int hmb, const uint8_t*
   a.ref1_v = ref1_v;
   a.bmode = bmode;
   a.t8 = t8;
+  if (mref4 && !bmode) {  // a reference per quadrant
+    launch_encode_inter_mixed(a, mref4, dim3(mb_row_grid(wmb * hmb), B), dim3(chroma_wave_grid(wmb * hmb), B),
+                              static_cast<hipStream_t>(stream));
+    return;
+  }
   hipLaunchKernelGGL(encode_inter_mb, dim3(mb_row_grid(wmb * hmb), B), dim3(64), 0, static_cast<hipStream_t>(stream), a);
   hipLaunchKernelGGL(encode_inter_chroma, dim3(chroma_wave_grid(wmb * hmb), B), dim3(64), 0, static_cast<hipStream_t>(stream), a);
 }
+#endif

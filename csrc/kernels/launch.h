@@ -64,6 +64,12 @@ void mivc_launch_p_part8(int B, int wmb, int hmb, const uint8_t* src_y, const ui
                          const int16_t* mv, const int16_t* pm, int* cost, uint8_t* pred, int16_t* mv8, const int* qp,
                          const int8_t* aq, int overhead, int min_satd, void* stream, const void* route, int nbuf,
                          const int* bits16, const uint8_t* dir16);
+// ---- h264_p_mixed.hip
+void mivc_launch_p_mixed_refs(int B, int wmb, int hmb, int nref, int16_t* mv, int16_t* mv8, int* cost, uint8_t* pred,
+                              const int16_t* xmv, const int* xcost, const uint8_t* xpred, int8_t* mref, int8_t* mref4,
+                              const int* qp, const int8_t* aq, const uint8_t* src0, const uint8_t* src,
+                              const uint8_t* ref, const uint8_t* hp, const int16_t* pm, const int16_t* scale,
+                              int overhead, int min_satd, void* stream, const void* route, int nbuf);
 // ---- h264_b.hip
 void mivc_launch_b_direct(int B, int wmb, int hmb, const void* col, const int* dsf, const int* direct_copy, int nref,
                           int16_t* dmv, int8_t* dref, int16_t* pm0, int16_t* pm1, void* stream, const void* route,
@@ -96,7 +102,7 @@ void mivc_launch_encode_inter(int B, int wmb, int hmb, const uint8_t* src_y, con
                               int bmode, int t8, const int16_t* mv8, void* stream, const int* w1, int nref,
                               const uint8_t* const* xref_u, const uint8_t* const* xref_v, const int8_t* mref,
                               const int* wp, int trellis, float trellis_lambda, const void* route, int nbuf,
-                              uint8_t* qp_flags, uint32_t* mask_pre);
+                              uint8_t* qp_flags, uint32_t* mask_pre, const int8_t* mref4);
 // ---- encode_intra.hip
 void mivc_launch_encode_intra(int B, int wmb, int hmb, const uint8_t* src_y, const uint8_t* src_u,
                               const uint8_t* src_v, uint8_t* rec_y, uint8_t* rec_u, uint8_t* rec_v, const int* qp,

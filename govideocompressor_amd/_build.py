@@ -126,7 +126,11 @@ def build_hip(nproc: int = 8) -> str:
     for s in srcs:
         o = os.path.join(BUILD, "hip", os.path.basename(s) + ".o")
         objs.append(o)
-        jobs.append(([HIPCC, *hip_flags, "-c", s, "-o", o], o, [s, *hdrs]))
+        # a unit that is another unit's text under a macro (encode_inter_mixed.hip) depends on it
+        with open(s) as f:
+            text = f.read()
+        incl = [x for x in srcs if x != s and f'#include "{os.path.basename(x)}"' in text]
+        jobs.append(([HIPCC, *hip_flags, "-c", s, "-o", o], o, [s, *incl, *hdrs]))
     host_flags = ["-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-D__HIP_PLATFORM_AMD__"]
     host_flags += [f"-I{p}" for p in _pybind_includes()] + ["-I/opt/rocm/include"]
     for s in binds:

@@ -212,6 +212,9 @@ H264_PARAMS = {
     "no-deblock": ("deblock", lambda v: not _flag(v)),
     "partitions": ("partitions", _partitions),
     "ref": ("refs", _int_in(1, 4)),
+    # a reference per 8x8 partition of a P macroblock (h264_p_mixed.hip); off unless asked for
+    "mixed-refs": ("mixed_refs", _flag),
+    "no-mixed-refs": ("mixed_refs", lambda v: not _flag(v)),
     "weightp": ("weightp", lambda v: _int_in(0, 2)(v) > 0),
     "weightb": ("weightb", _flag),
     "no-weightb": ("weightb", lambda v: not _flag(v)),

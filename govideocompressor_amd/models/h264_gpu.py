@@ -242,6 +242,13 @@ class H264Params:
     ref_range: int = 4
     # content suite (profiles/r4_knob_sweep.md): 3000 is -0.67 % BD-rate and +1.5 % fps vs 1500
     ref_gate: int = 3000
+    # x264 --mixed-refs (on from its "fast" preset; opt-in here until measured): a reference per
+    # 8x8 quadrant of a P macroblock.  p_mixed_refs (csrc/kernels/h264_p_mixed.hip) takes
+    # me_ref_select's place and prices, for every MB that had a farther picture searched (it
+    # passed ref_gate), a quadrant-wise choice among the searched pictures beside the list-0[0]
+    # decision and the 16x16 farther pictures.  Needs several references and the 8x8 partitions
+    # (both CABAC only); P pictures only.
+    mixed_refs: bool = False
     # slices per picture (x264 --slices): whole MB rows each.  The GPU arithmetic coder codes
     # one slice per lane, so S slices give S times the independent serial chains per picture
     # (and the intra wavefront restarts at every slice); each slice costs a header and the
@@ -284,6 +291,9 @@ class H264Params:
     def eff_weightp(self) -> bool:
         return bool(self.weightp and self.cabac)
 
+    def eff_mixed_refs(self) -> bool:
+        return bool(self.mixed_refs and self.eff_refs() > 1 and self.eff_partitions())
+
     def eff_t8x8(self) -> bool:
         return bool(self.t8x8 and self.cabac)
 
@@ -306,6 +316,7 @@ class H264Params:
         nb = self.eff_bframes()
         return (("High CABAC 8x8dct" if self.eff_t8x8() else "Main CABAC") + (" i8x8" if self.eff_t8x8() and self.i8x8 else "")
                 + (" p8x8" if self.eff_partitions() else "") + (" b8x8" if self.eff_partitions() and self.bpartitions and self.eff_bframes() else "") + (f" ref{self.eff_refs()}" if self.eff_refs() > 1 else "")
+                + (" mixed-refs" if self.eff_mixed_refs() else "")
                 + (" weightp" if self.eff_weightp() else "")
                 + (f" {nb}B" + (" b-adapt" if self.b_adapt else "") + (" b-pyramid" if self.eff_pyramid() else "")
                    + f" {self.direct}-direct" if nb else "")
@@ -515,6 +526,8 @@ class GpuH264Encoder:
             self.xcost = torch.zeros((K, B, nmb), dtype=i32, device=dev)
             self.xpred = torch.zeros((K, B, nmb, 256), dtype=u8, device=dev)
             self.xpm = torch.zeros((B, nmb, 2), dtype=i16, device=dev)
+        # x264 --mixed-refs: the reference of every 8x8 quadrant of a P MB (p_mixed_refs)
+        self.mref4 = torch.zeros((B, nmb, 4), dtype=torch.int8, device=dev) if params.eff_mixed_refs() else None
         if self.nb:
             # B pictures: the list-1 search, temporal direct vectors and the mode decision
             self.mv1 = torch.zeros((B, nmb, 2), dtype=i16, device=dev)
@@ -559,6 +572,7 @@ class GpuH264Encoder:
         self._inflight: list = []             # encode_async batches not yet finished (oldest first)
         self.p_intra_mbs = torch.zeros((), dtype=torch.int64, device=dev)  # intra MBs coded in P frames
         self.far_ref_mbs = torch.zeros((), dtype=torch.int64, device=dev)  # P MBs choosing RefPicList0[1 ..]
+        self.mixed_ref_mbs = torch.zeros((), dtype=torch.int64, device=dev)  # P MBs whose quadrants differ in reference
         self.sfix_mbs = torch.zeros((), dtype=torch.int64, device=dev)  # fast spatial direct: MBs re-predicted
         self.sconv_mbs = torch.zeros((), dtype=torch.int64, device=dev)  # ... and MBs made explicit
         # temporal direct under a pyramid: B MBs with a quadrant that has no direct prediction
@@ -841,21 +855,35 @@ class GpuH264Encoder:
                                     P(self.xpred[k - 1]), 0, P(self.qp), int(self.p.ref_range), self.p.subpel, s,
                                     hpp, aq, 1, self.p.p_early_sad, P(self.me_cost), self._ref_gate(),
                                     P(self.prev_mv), rt, NB, k, SK["P"])
-                    self.hip.me_ref_select(B, wmb, hmb, nr, P(self.mv), mv8, P(self.me_cost), P(self.pred),
-                                           P(self.xmv), P(self.xcost), P(self.xpred), P(self.mref), P(self.qp), aq,
-                                           s, rt)
+                    if self.mref4 is not None:
+                        # a reference per quadrant: the choice of me_ref_select plus the quadrant-wise one
+                        # (its mvds priced against prev_mv, by now this picture's own 16x16 vectors,
+                        # as the farther searches' were)
+                        self.hip.p_mixed_refs(B, wmb, hmb, nr, P(self.mv), mv8, P(self.me_cost), P(self.pred),
+                                              P(self.xmv), P(self.xcost), P(self.xpred), P(self.mref), P(self.mref4),
+                                              P(self.qp), aq, sy_me, sy, py, hpp, P(self.prev_mv),
+                                              st["xscale256"].data_ptr(), int(self.p.part_overhead),
+                                              int(self.p.part_min_satd), s, rt, NB)
+                        self.mixed_ref_mbs += ((self.mref4 != self.mref4[:, :, :1]).any(dim=2) & st["pmask"][:, None]).sum()
+                    else:
+                        self.hip.me_ref_select(B, wmb, hmb, nr, P(self.mv), mv8, P(self.me_cost), P(self.pred),
+                                               P(self.xmv), P(self.xcost), P(self.xpred), P(self.mref), P(self.qp),
+                                               aq, s, rt)
                     self.far_ref_mbs += ((self.mref > 0) & st["pmask"][:, None]).sum()
             else:
                 self.mref.zero_()
+                if self.mref4 is not None:
+                    self.mref4.zero_()
             if cut is not None:
                 self.intra_cost.masked_fill_(cut[:, None], -1)  # intra beats any inter cost
+            mkw = {} if self.mref4 is None else {"mref4": P(self.mref4)}
             with stt("inter"):
                 self.hip.encode_inter(B, wmb, hmb, sy, su, sv, py, pu, pv, py, pu, pv, P(self.pred), P(self.mv),
                                       P(self.me_cost), P(self.intra_cost), P(self.qp), cqo, P(hdr), P(coef),
                                       P(self.nz), P(self.intra_flag), P(self.intra_count), s, aq,
                                       t8=int(self.p.eff_t8x8()), mv8=mv8, mref=P(self.mref), wp=wp,
                                       trellis=int(self.p.trellis), trellis_lambda=float(self.p.trellis_lambda),
-                                      route=rt, nbuf=NB, **ikw)
+                                      route=rt, nbuf=NB, **ikw, **mkw)
         if st["B"]:
             br = self.p.b_me_range
             spatial = self.p.direct == "spatial"
@@ -1067,6 +1095,8 @@ class GpuH264Encoder:
         rt_d = torch.from_numpy(rt.view(np.uint8).reshape(F, B * ROUTE_DTYPE.itemsize).copy()).to(dev)
         kinds_d = torch.from_numpy(np.ascontiguousarray(rt["kind"])).to(dev)
         xs_d = torch.from_numpy(xscale).to(dev)
+        # the same ratios in 1/256 units, for the integer scaling of p_mixed_refs
+        xs256_d = torch.from_numpy(np.rint(xscale * 256.0).astype(np.int16)).to(dev) if self.mref4 is not None else None
         ss_d = torch.from_numpy(sscale).to(dev)
         # (all zero -- no pyramid -- is the identity: no table, b_direct_mv's plain path)
         cmap_d = torch.from_numpy(cmap).to(dev) if cmap.any() else None
@@ -1090,6 +1120,7 @@ class GpuH264Encoder:
             st = dict(route=rt_d[t].data_ptr(), cmap=cmap_d[t].data_ptr() if cmap_d is not None else 0,
                       P=bool((k == 0).any()), B=bool((k == 1).any()),
                       pmask=pmask_d[t], bmask=bmask_d[t], maxn0=int(n0p.max()) if n0p.size else 1, xscale=xs_d[t],
+                      xscale256=None if xs256_d is None else xs256_d[t],
                       deblock=bool((rt["flags"][t] & SF_DEBLOCK).any()), ref=bool((rt["flags"][t] & SF_REF).any()),
                       wp=None, wp_src=None, col_src=None, col_dst=None, kinds=k, sscale=ss_d[t])
             if t in cofs:
@@ -1773,13 +1804,14 @@ class GpuH264Encoder:
         # reuse the accumulators, and note which groups last used the two CABAC rings
         B_ = B
         counters = torch.stack([self.p_intra_mbs, self.far_ref_mbs, self.sfix_mbs, self.sconv_mbs,
-                                self.una_mbs]).to(torch.int64)
+                                self.una_mbs, self.mixed_ref_mbs]).to(torch.int64)
         self.p_intra_mbs.zero_()
         self.far_ref_mbs.zero_()
+        self.mixed_ref_mbs.zero_()
         self.sfix_mbs.zero_()
         self.sconv_mbs.zero_()
         self.una_mbs.zero_()
-        h_counters = torch.empty((5,), dtype=torch.int64).pin_memory()
+        h_counters = torch.empty((6,), dtype=torch.int64).pin_memory()
         h_counters.copy_(counters, non_blocking=True)
         h_sse = h_ssim = None
         if metrics:
@@ -1824,6 +1856,9 @@ class GpuH264Encoder:
                 if self.nref > 1 and n_p:
                     # share of P-picture MBs (inter decisions before the intra override) on a farther picture
                     self.stats["p_far_ref_ratio"] = float(c[1]) / (n_p * self.nmb)
+                if self.mref4 is not None:
+                    # P MBs (inter decisions before the intra override) whose quadrants differ in reference
+                    self.stats["mixed_ref_mbs"] = int(c[5])
                 nbp = sum(1 for plan in plans for pic in plan if pic.kind == "B")
                 self.stats["b_ratio"] = nbp / float(B_ * F)
                 if nbp and self.p.direct == "spatial":

@@ -58,6 +58,7 @@ H264 = {
     "MIVC_REFS": "refs",
     "MIVC_REF_RANGE": "ref_range",
     "MIVC_REF_GATE": "ref_gate",
+    "MIVC_MIXED_REFS": "mixed_refs",
     "MIVC_SLICES": "slices",
     "MIVC_AQ_MODE": "aq_mode",
 }

@@ -40,6 +40,8 @@ CONFIGS = {
     "bias100": dict(b_adapt=1, b_bias=100),
     "badapt_ng": dict(b_adapt=1, badapt_guard=False),  # without x264's intra-MB guards
     "slices4": dict(slices=4),
+    # x264 --mixed-refs: a reference per 8x8 partition of a P MB (profiles/h264_mixed_refs.md)
+    "mixedrefs": dict(mixed_refs=True),
     "noseed": dict(lowres_seed=False),
     "trellis1": dict(trellis=1),  # round 3's trellis scope (4x4 luma only)
     "bf0": dict(bframes=0),       # P pictures only
@@ -205,6 +207,8 @@ def run(args):
                           direct_unavail_ratio=stats.get("direct_unavail_ratio"))
                 if "weightb_pictures" in stats:
                     pt["weightb_pictures"] = stats["weightb_pictures"]
+                if "mixed_ref_mbs" in stats:  # P MBs whose quadrants differ in reference (last batch)
+                    pt["mixed_ref_mbs"] = int(stats["mixed_ref_mbs"])
                 if "tskip_tus" in stats:  # 4x4 TUs coded with transform_skip_flag 1: intra luma, intra chroma, inter chroma
                     pt["tskip_tus"] = list(stats["tskip_tus"])
                 if getattr(enc, "stage_ms", None):  # MIVC_STAGE_TIMING=1: device time per stage of this call
